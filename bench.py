@@ -3,7 +3,12 @@
 steps) on MI355X, scenes/s at batch 64 per GPU (BASELINE.json metric / configs[1], weak scaling
 over 1/2/4/8 GPUs with one RCCL all_gather of the predicted trajectories per step).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the K steps, writes
+the outputs of the last timed step when ``--dump-outputs DIR`` is given (``DIR/trajectory.npy``: the float32
+trajectories the timed step returned, [B x N, 8, 3]; the inputs are seeded, so two builds can be compared output for
+output) and prints the result line. Every other leg listed below (marked ``--full``) runs only with ``--full``.
 
 With ``--gpus N > 1`` and no ``$WORLD_SIZE`` the script launches N rank processes itself
 (torchrun-style: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in their
@@ -14,12 +19,14 @@ launcher's environment; a ``--gpus`` that disagrees with ``$WORLD_SIZE`` is an e
 A step = one forward of B synthetic scenes resident in HBM (+ the all_gather when N > 1). ``--in-flight L``
 (default 3) keeps L steps in flight per GPU (diffusiondrive_amd/model.py InFlightPlanner); the timed region
 still brackets all K steps completely.
-Rank 0 prints ONE JSON line. Besides the contract fields it reports:
+Rank 0 prints ONE JSON line: the contract fields (``metric``, ``value``, ``unit``, ``higher_is_better``, ``dtype``,
+``ms_per_step`` = wall time of the timed region / K, ...), ``config``, ``numerics_flags`` and
   * ``median_ms_per_step``: median step interval from the completion events (HIP events on the lanes' streams,
     end times sorted on the device clock, windows of ``in_flight`` completions: ``completion_intervals``);
     ``median_batch_latency_ms``: median start -> end of one step's forward on its lane (with ``--in-flight N`` > 1,
     N batches share the device, so a batch takes longer while the steps complete faster); ``scenes_resident`` =
-    batch x in_flight;
+    batch x in_flight.
+With ``--full`` the same line also carries (each a run or a check of its own after the timed steps):
   * ``in_flight_1``: the same workload one batch at a time - the strict "scenes/s at batch 64" figure;
   * ``gather_check``: every rank's slice of the all_gather output equals its own forward (N > 1: the C3 workload,
     shards of one seeded global batch), and shard 0's waypoint L2 against the reference golden;
@@ -90,6 +97,12 @@ def parse():
     p.add_argument("--warmup", type=int, default=10)
     p.add_argument("--batch", type=int, default=64, help="scenes per GPU")
     p.add_argument("--denoise-steps", type=int, default=2)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the last timed step's outputs to DIR/<name>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run every secondary leg: gather / golden check, roofline replay, "
+                        "batch 1, fp32 leg, in-flight 1, H2D-inclusive, CPU baseline (--no-compare / --no-cpu-baseline "
+                        "trim it)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-threads", default="8", help="extra thread counts of the CPU-oracle baseline beside the job's "
                                                        "CPU share (BASELINE.md: n = 8 and n = all cores; 3 reps each)")
@@ -217,14 +230,62 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     scenes_per_s = B * world * args.steps / elapsed
     torch.cuda.synchronize()
-    traj_gpu = out[rank * B:(rank + 1) * B].detach().cpu().numpy()
-    gather_ok = gather_slices_ok(out, lane_steps.last_local, rank, B, dist, dev)
-    gathered = out.detach().cpu().numpy()
-    shard0_golden_l2 = golden_l2(gathered, args.arch, B, args.denoise_steps) if B == 64 else None
+    gathered = out.detach().cpu().numpy()  # what the last timed step returned: every rank's trajectories
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"trajectory": gathered})
     num_flags = pl.numerics_flags()
     if num_flags:
         print(f"[bench] WARNING: numerics flags {num_flags:#x} raised (f16x3 overflow): result untrustworthy",
               file=sys.stderr)
+    result = {
+        "metric": METRIC,
+        "value": round(scenes_per_s, 3),
+        "unit": "scenes/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3),
+        "median_ms_per_step": round(med, 3),
+        "median_batch_latency_ms": round(lat_med, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": DTYPE[args.gemm],
+        "data": "synthetic (seeded camera/LiDAR/status/noise; seeded random weights of the reference architecture)",
+        "config": {
+            "workload": f"DiffusionDrive eval forward: {args.arch} camera + ResNet-34 LiDAR-BEV backbone, "
+                        f"GPT fusion x4, tf decoder, truncated diffusion decoder {args.denoise_steps} DDIM steps x 2 "
+                        f"layers, 20 modes; batch {B} scenes per GPU",
+            "batch_per_gpu": B,
+            "global_batch": B * world,
+            "denoise_steps": args.denoise_steps,
+            "parallelism": f"dp{world} (scene sharding, RCCL all_gather of trajectories)",
+            "graph": True,
+            "in_flight": args.in_flight,
+            "in_flight_note": "batches in flight per GPU: InFlightPlanner lanes (handles with the same weights, each "
+                              "a single-stream captured forward replayed on a stream of its own); consecutive steps "
+                              "go to consecutive lanes; every step's forward runs whole inside the timed region. "
+                              "1 = one forward at a time on a default (two-stream) handle",
+            "gemm": args.gemm,
+            "heads": False,
+            "heads_note": "the timed forward is the waypoint path (trajectory out); the BEV-semantic and agent "
+                          "heads (off that path, 0.33 GFLOP/scene, SURVEY §8a-a10) are not run - parity tests run them",
+        },
+        "numerics_flags": num_flags,
+        "scenes_resident": B * args.in_flight,
+        "full": bool(args.full),
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- everything below runs with --full only
+    traj_gpu = gathered[rank * B:(rank + 1) * B]
+    gather_ok = gather_slices_ok(out, lane_steps.last_local, rank, B, dist, dev)
+    shard0_golden_l2 = golden_l2(gathered, args.arch, B, args.denoise_steps) if B == 64 else None
 
     # ---- roofline of the dominant kernel: a profiled single-stream replay of the same workload
     # (HIP events around every launch on the stream it is issued to)
@@ -322,40 +383,7 @@ def main():
             traffic = None
     algo_bytes = st["bytes"] / max(st["launches"], 1)
 
-    result = {
-        "metric": METRIC,
-        "value": round(scenes_per_s, 3),
-        "unit": "scenes/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "median_ms_per_step": round(med, 3),
-        "median_batch_latency_ms": round(lat_med, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": DTYPE[args.gemm],
-        "data": "synthetic (seeded camera/LiDAR/status/noise; seeded random weights of the reference architecture)",
-        "config": {
-            "workload": f"DiffusionDrive eval forward: {args.arch} camera + ResNet-34 LiDAR-BEV backbone, "
-                        f"GPT fusion x4, tf decoder, truncated diffusion decoder {args.denoise_steps} DDIM steps x 2 "
-                        f"layers, 20 modes; batch {B} scenes per GPU",
-            "batch_per_gpu": B,
-            "global_batch": B * world,
-            "denoise_steps": args.denoise_steps,
-            "parallelism": f"dp{world} (scene sharding, RCCL all_gather of trajectories)",
-            "graph": True,
-            "in_flight": args.in_flight,
-            "in_flight_note": "batches in flight per GPU: InFlightPlanner lanes (handles with the same weights, each "
-                              "a single-stream captured forward replayed on a stream of its own); consecutive steps "
-                              "go to consecutive lanes; every step's forward runs whole inside the timed region. "
-                              "1 = one forward at a time on a default (two-stream) handle",
-            "gemm": args.gemm,
-            "heads": False,
-            "heads_note": "the timed forward is the waypoint path (trajectory out); the BEV-semantic and agent "
-                          "heads (off that path, 0.33 GFLOP/scene, SURVEY §8a-a10) are not run - parity tests run them",
-        },
+    result.update({
         "roofline": {
             "kernel": KERNEL_DESC[main_k],
             "bound": "mfma",
@@ -402,14 +430,12 @@ def main():
                     "issues (value_proj only at the sampled taps, bev_proj keyval half at 8x8)",
         },
         "decoder_cross_attention": value_proj,
-        "numerics_flags": num_flags,
-        "scenes_resident": B * args.in_flight,
         "gather_check": {"gathered_rows": int(gathered.shape[0]), "every_rank_slice_equals_local": gather_ok,
                          "shard0_waypoint_l2_vs_golden": shard0_golden_l2,
                          "note": "each rank's slice of the all_gather output equals its own forward bit for bit "
                                  "(MIN over ranks); shard 0 = scenes 0..63 of the seeded global batch vs the "
                                  "reference golden tests/golden/ref_b64_s1234.npz"},
-    }
+    })
     if h2d is not None:
         result["h2d_included"] = h2d
     if one_at_a_time is not None:
@@ -436,6 +462,22 @@ def main():
         print(json.dumps(result), flush=True)
     if dist is not None:
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6  # array payload of one dump: under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, arrays):
+    """Write what the last timed step returned as ``out_dir/<name>.npy`` (float32), at most DUMP_LIMIT_BYTES in all:
+    an array over its share of the limit is written as a fixed seeded sample of its flattened elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) // 4
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def batch1_leg(cfg, sd, feats, noise, args, dev, reps=60):
@@ -761,6 +803,8 @@ def plumbing(args, world, rank):
         t = torch.tensor([el], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         el = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"trajectory": out.numpy()})
     ranks_seen = sorted({int(v) // 1000 for v in out[:, 0, 0].tolist()})
     # every rank's slice of the last gather came from the same step (collectives issued in step order on all ranks)
     steps_seen = sorted({int(v) % 1000 for v in out[:, 0, 0].tolist()})

@@ -48,6 +48,18 @@ def test_single_rank_plumbing():
     assert j["n_gpus"] == 1 and j["config"]["global_batch"] == 2
 
 
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    """--dump-outputs DIR: the rows the last timed step returned, as DIR/trajectory.npy in float32 (stand-in step:
+    every value of step k is k), and the result line carries ms_per_step for the --steps it was given."""
+    import numpy as np
+    r = _run(["--cpu-plumbing", "--steps", "3", "--warmup", "1", "--batch", "2", "--dump-outputs", str(tmp_path / "o")])
+    assert r.returncode == 0, r.stderr
+    j = json.loads(r.stdout.strip().splitlines()[-1])
+    assert j["steps"] == 3 and j["ms_per_step"] >= 0
+    t = np.load(tmp_path / "o" / "trajectory.npy")
+    assert t.dtype == np.float32 and t.shape == (2, 8, 3) and np.all(t == 4.0)
+
+
 def test_gpus2_three_lanes_in_flight_plumbing():
     """bench.py's lane path at --in-flight 3 over gloo with two ranks: the bench's own LaneSteps drives an
     InFlightPlanner of three stand-in lanes (its real round-robin), every step all-gathers on its lane's stream, and

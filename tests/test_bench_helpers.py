@@ -53,6 +53,23 @@ def test_value_proj_algo_bytes_counts_each_neighbourhood_pixel_once():
     assert got == (25 + 5) * 1024 + 9 * 256 * 256 * 4
 
 
+def test_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: a small array is written whole as float32; one over its share of the byte limit is written
+    as the same seeded sample of its elements on every call."""
+    b = _bench()
+    a = np.arange(48, dtype=np.float64).reshape(2, 8, 3)
+    b.dump_outputs(str(tmp_path / "d"), {"trajectory": a})
+    got = np.load(tmp_path / "d" / "trajectory.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 8, 3) and np.array_equal(got, a)
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 2 * 10 * 4)  # two arrays, 10 float32 each
+    big = np.arange(100, dtype=np.float32)
+    for d in ("e", "f"):
+        b.dump_outputs(str(tmp_path / d), {"x": big, "y": a})
+    x1, x2 = np.load(tmp_path / "e" / "x.npy"), np.load(tmp_path / "f" / "x.npy")
+    assert x1.shape == (10,) and np.array_equal(x1, x2) and np.all(np.diff(x1) > 0) and set(x1) <= set(big)
+    assert np.load(tmp_path / "e" / "y.npy").shape == (10,)
+
+
 def test_gather_slices_ok_detects_a_wrong_slice():
     """bench.gather_slices_ok on one rank: the rank's own slice of the gathered rows against its local output."""
     import torch

@@ -6,7 +6,7 @@
 <pmc_summary>.json is tools/pmc_round2.py's output over tools/gpu_pmc_round2.sh's passes (separate rocprofv3
 --pmc FETCH_SIZE / WRITE_SIZE runs over the bench workload, single-stream replays). HBM bytes per dispatch =
 2 x FETCH_SIZE + WRITE_SIZE (KB; gfx950 reports half the bytes of 16-B/lane streaming reads, MI355X_MICROARCH.md).
-With --bench (a bench.py JSON line of the same build) the algorithmic bytes per launch and the
+With --bench (a ``bench.py --full`` JSON line of the same build) the algorithmic bytes per launch and the
 traffic / algorithmic ratio are recorded beside it.
 """
 import argparse
