@@ -185,7 +185,7 @@ def denorm_odo(x):
 def sine_embed(pos, hidden_dim=64):
     """gen_sineembed_for_position (blocks.py:22-40): output cat(pos_y, pos_x)."""
     half = hidden_dim // 2
-    dim_t = torch.arange(half, dtype=torch.float32)
+    dim_t = torch.arange(half, dtype=pos.dtype)
     dim_t = 10000 ** (2 * (dim_t // 2) / half)
     xe = pos[..., 0] * (2 * math.pi)
     ye = pos[..., 1] * (2 * math.pi)
@@ -196,11 +196,11 @@ def sine_embed(pos, hidden_dim=64):
     return torch.cat((py, px), -1)
 
 
-def timestep_embed(t, dim=256):
-    """SinusoidalPosEmb (conditional_unet1d.py:53-66) for an int64 timestep vector."""
+def timestep_embed(t, dim=256, dtype=torch.float32):
+    """SinusoidalPosEmb (conditional_unet1d.py:53-66) for an int64 timestep vector, in ``dtype``."""
     half = dim // 2
     e = math.log(10000) / (half - 1)
-    e = torch.exp(torch.arange(half) * -e)
+    e = torch.exp(torch.arange(half, dtype=dtype) * -e)
     e = t[:, None] * e[None, :]
     return torch.cat((e.sin(), e.cos()), -1)
 
@@ -209,11 +209,14 @@ class DDIM:
     """diffusers DDIMScheduler restated for the reference's use (transfuser_model_v2.py:447-451;
     add_noise :595-597; step eta=0, prediction_type='sample', clip_sample=True :634-636)."""
 
-    def __init__(self, num_train=1000, beta_start=1e-4, beta_end=0.02):
+    def __init__(self, num_train=1000, beta_start=1e-4, beta_end=0.02, dtype=torch.float32):
+        # alphas_cumprod is a float32 table of the scheduler whatever the sample's dtype (a constant of the model, as
+        # the weights are): ``dtype`` only widens it, so a float64 run does its own arithmetic (1 - a, the roots,
+        # the step) in float64 on the same schedule. One ulp of alphas_cumprod[8] moves the waypoints by 1e-4.
         betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train, dtype=torch.float32) ** 2
         self.num_train = num_train
-        self.ac = torch.cumprod(1.0 - betas, 0)
-        self.final = torch.tensor(1.0)
+        self.ac = torch.cumprod(1.0 - betas, 0).to(dtype)
+        self.final = torch.tensor(1.0, dtype=dtype)
 
     def add_noise(self, x0, noise, t):
         a = self.ac[t]
@@ -272,7 +275,7 @@ def trajectory_head(ego_q, agents_q, bev, sd, cfg, noise, steps=None, taps=None,
     steps = steps or cfg.denoise_steps
     p = "_trajectory_head"
     B = ego_q.shape[0]
-    sched = DDIM(cfg.num_train_timesteps)
+    sched = DDIM(cfg.num_train_timesteps, dtype=noise.dtype)
     if schedule == "vanilla":
         step_ratio = cfg.num_train_timesteps // steps
         roll = (np.arange(0, steps) * step_ratio)[::-1].copy().astype(np.int64)
@@ -295,7 +298,7 @@ def trajectory_head(ego_q, agents_q, bev, sd, cfg, noise, steps=None, taps=None,
         tf = linear(emb, sd, p + ".plan_anchor_encoder.0")
         tf = layer_norm(F.relu(tf), sd, p + ".plan_anchor_encoder.2")
         tf = linear(tf, sd, p + ".plan_anchor_encoder.3")
-        te = timestep_embed(torch.full((B,), int(k), dtype=torch.int64))
+        te = timestep_embed(torch.full((B,), int(k), dtype=torch.int64), dtype=noise.dtype)
         te = linear(mish(linear(te, sd, p + ".time_mlp.1")), sd, p + ".time_mlp.3").view(B, 1, -1)
         cur = pts
         for l in range(cfg.num_diff_layers):
@@ -421,7 +424,10 @@ def transfuser_loss(targets, pred, cfg):
 
 # --------------------------------------------------------------------------- full model
 class OracleModel:
-    """fp32 CPU restatement of V2TransfuserModel.forward in eval mode (transfuser_model_v2.py:98-162)."""
+    """fp32 CPU restatement of V2TransfuserModel.forward in eval mode (transfuser_model_v2.py:98-162).
+
+    The arithmetic follows the dtype of the state dict and the inputs: a float64 dict with float64 inputs runs the
+    whole forward in float64 (the yardstick for the fp32 oracle's own rounding; tests/test_decoder_edges.py)."""
 
     def __init__(self, state_dict: Mapping[str, np.ndarray], cfg: TransfuserConfig = None):
         self.cfg = cfg or TransfuserConfig()

@@ -496,13 +496,31 @@ def test_bev_sample_attn(gpu):
     close(out, ref, 1e-5)
 
 
-@pytest.mark.parametrize("Lq,Lk", [(31, 31), (31, 65), (20, 30), (20, 1), (5, 128)])
-def test_mha_small(gpu, Lq, Lk):
-    B, nh, hd = 3, 8, 32
+# (B, nh, hd, Lq, Lk). The first five stage a whole head in LDS (mha_head_kernel); the rest need more than 64 KiB for
+# that and take the one-wave-per-query-row fallback (mha_small_kernel): Lk = 128 / 127 / 65 / 64 (the second key of a
+# lane present, partly present, first present, absent), item counts B * nh * Lq that are no multiple of the 4 waves
+# of a workgroup (210, 70: an inactive wave in the last one) and hd = 48 (the d < hd guard of the P.V pass).
+MHA_SMALL_HEAD = [(3, 8, 32, 31, 31), (3, 8, 32, 31, 65), (3, 8, 32, 20, 30), (3, 8, 32, 20, 1), (3, 8, 32, 5, 128)]
+MHA_SMALL_FALLBACK = [(1, 3, 32, 70, 127), (1, 2, 32, 64, 128), (1, 2, 32, 130, 65), (1, 2, 32, 150, 64),
+                      (1, 1, 48, 70, 127)]
+
+
+def _mha_lds_bytes(hd, Lq, Lk):
+    """launch_mha_small's LDS need of the whole-head form (decoder.hip)."""
+    return 4 * (Lq * (hd + 1) + Lk * (hd + 1) + Lk * hd + Lq * (Lk + 1))
+
+
+@pytest.mark.parametrize("B,nh,hd,Lq,Lk", MHA_SMALL_HEAD + MHA_SMALL_FALLBACK,
+                         ids=[f"{c[3]}-{c[4]}" for c in MHA_SMALL_HEAD] +
+                             ["fallback-" + "-".join(map(str, c)) for c in MHA_SMALL_FALLBACK])
+def test_mha_small(gpu, B, nh, hd, Lq, Lk):
+    # there is no route string for this op: the kernel taken follows from the LDS need alone
+    fallback = (B, nh, hd, Lq, Lk) in MHA_SMALL_FALLBACK
+    assert (_mha_lds_bytes(hd, Lq, Lk) > 64 * 1024) == fallback
     q, k, v = rnd(B, Lq, nh * hd, seed=24), rnd(B, Lk, nh * hd, seed=25), rnd(B, Lk, nh * hd, seed=26)
-    qh = q.view(B, Lq, nh, hd).transpose(1, 2)
-    kh = k.view(B, Lk, nh, hd).transpose(1, 2)
-    vh = v.view(B, Lk, nh, hd).transpose(1, 2)
+    qh = q.double().view(B, Lq, nh, hd).transpose(1, 2)  # the reference in float64
+    kh = k.double().view(B, Lk, nh, hd).transpose(1, 2)
+    vh = v.double().view(B, Lk, nh, hd).transpose(1, 2)
     ref = (torch.softmax(qh @ kh.transpose(-1, -2) / np.sqrt(hd), -1) @ vh).transpose(1, 2).reshape(B, Lq, nh * hd)
     out = torch.empty(B, Lq, nh * hd, device=DEV)
     qd, kd, vd = g(q), g(k), g(v)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from decoder_edge_util import check_gathered_taps
 from golden_util import compare_tap, golden_files, golden_files_r50, load, waypoint_l2
 
 pytestmark = pytest.mark.gpu
@@ -279,32 +280,10 @@ def test_gathered_value_rows_match_dense_map(gpu_model):
         pts = gpu_model.tap("pts", (B * Q * P, 2)).double().cpu().numpy()
     finally:
         gpu_model.set_gemm_mode("fp32")
-    # tap geometry (float32 arithmetic as the kernel / F.grid_sample)
-    p32 = pts.astype(np.float32)
-    ix = ((p32[:, 1] / np.float32(32) + 1) * np.float32(HB) - 1) / 2
-    iy = ((p32[:, 0] / np.float32(32) + 1) * np.float32(HB) - 1) / 2
-    x0, y0 = np.floor(ix).astype(np.int64), np.floor(iy).astype(np.int64)
-    b = np.arange(B * Q * P) // (Q * P)
-    pix = []
-    for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1)):
-        yy, xx = y0 + dy, x0 + dx
-        ok = (yy >= 0) & (yy < HB) & (xx >= 0) & (xx < HB)
-        pix.append(np.where(ok, (b * HB + yy) * HB + xx, -1))
-    pix = np.stack(pix, 1).reshape(-1)
-    assert (pix < 0).any() and (pix >= 0).any()
-    for s_ in range(B):
-        tp = pix[s_ * cap:(s_ + 1) * cap]
-        uniq = np.unique(tp[tp >= 0])
-        rs = rows[s_ * cap:(s_ + 1) * cap]
-        assert np.array_equal(rs[:len(uniq)], uniq) and (rs[len(uniq):] == -1).all(), s_
-        assert counts[s_] == len(uniq), (s_, counts[s_], len(uniq))  # the compacted launch's row counts
-    assert np.array_equal(slots < 0, pix < 0)
-    live = slots >= 0
-    assert np.array_equal(rows[slots[live]], pix[live])
-    used = rows >= 0
-    ref = dense[rows[used]]
-    err = np.abs(vals[used] - ref).max() / max(1.0, np.abs(ref).max())
-    assert err <= TAP_TOL, err
+    # tap geometry, row lists, counts, slots and the live rows against the dense map: the shared helper (also applied
+    # to every (step, layer) of the doctored cases in test_decoder_edges_gpu.py)
+    padded, live, _ = check_gathered_taps(pts, rows, slots, counts, vals, dense, B, TAP_TOL)
+    assert padded > 0 and live > 0
 
 
 def test_decoder_megakernel_matches_unfused_chain(gpu_model, seeded_sd, monkeypatch):
