@@ -738,7 +738,8 @@ class Model {
           v.part = buf("vproj_upart", (size_t)us * MR * d);
         }
       }
-      launch("value_proj", fl, [&] { launch_vproj(v, st); });
+      launch("value_proj", fl, [&] { launch_vproj(v, st); }, nullptr, -1.0,
+             v.union_stage ? "form=union" : "form=gathered");
       return;
     }
     struct ClassScope {
@@ -746,7 +747,7 @@ class Model {
       ClassScope(const char*& cc, const char* v) : c(cc) { c = v; }
       ~ClassScope() { c = nullptr; }
     } cls(force_class, "value_proj");
-    launch("conv_x3", fl, [&] { launch_conv_gemm(a, st); }, &a);
+    launch("conv_x3", fl, [&] { launch_conv_gemm(a, st); }, &a, -1.0, "form=conv_x3");
   }
 
   // TrajectoryHead.forward_test (:578-641) as 1 + 2 x steps x 2 launches: the DDIM start + first taps, then
@@ -866,7 +867,7 @@ class Model {
         // fp32 heads, 2 x rows x sum(K x N)
         double kn = 7.0 * d * d + 2.0 * d * 1024 + (double)d * (P + 1 + 3 * P);
         if (l == 0) kn += 512.0 * d + (double)d * d;
-        launch("decoder", 2.0 * R * kn, [&] { launch_decoder_mk(m, st); });
+        launch("decoder", 2.0 * R * kn, [&] { launch_decoder_mk(m, st); }, nullptr, -1.0, groups_note(m.groups));
         reg_last = m.reg_out;
         cls_last = m.cls_out;
       }
@@ -1060,8 +1061,13 @@ class Model {
     }
   }
 
+  // the chosen route as a note of the profiling log: workgroups per scene of the two megakernels
+  static const char* groups_note(int g) { return g == 4 ? "groups=4" : (g == 2 ? "groups=2" : "groups=1"); }
+
+  // `note` (profiling only): appended to the launch's detail in $DDMI_LAUNCH_LOG (groups= / form=)
   template <class F>
-  void launch(const char* name, double flops, F&& f, const ConvArgs* shape = nullptr, double bytes = -1.0) {
+  void launch(const char* name, double flops, F&& f, const ConvArgs* shape = nullptr, double bytes = -1.0,
+              const char* note = nullptr) {
     if (!profiling) {
       f();
       return;
@@ -1088,8 +1094,9 @@ class Model {
       detail = "M=" + std::to_string((int64_t)c.Nimg * c.Ho * c.Wo) + " N=" + std::to_string(c.Cout) +
                " K=" + std::to_string(c.KH * c.KW * c.Cin) + " k=" + std::to_string(c.KH) + " s=" +
                std::to_string(c.stride) + " z=" + std::to_string(c.batch) + " HW=" + std::to_string(c.H) + "x" +
-               std::to_string(c.W);
+               std::to_string(c.W) + " cfg=" + last_conv_config();  // read after f(): the dispatcher's choice
     }
+    if (note) detail += (detail.empty() ? "" : " ") + std::string(note);
     pending.push_back({name, flops, bytes >= 0.0 ? bytes : (shape ? conv_algo_bytes(*shape) : 0.0), a, b, detail});
   }
 
@@ -1727,7 +1734,8 @@ class Model {
         // 2 x rows x sum(K x N): per layer q|k|v, 2 out_proj, cross q, FFN (+ the attention products), hoists
         const double kn = 3.0 * (3584.0 * d) + 4.0 * d * d + 4.0 * d * d;
         const double att = 3.0 * 8 * (31.0 * 31 + 31.0 * 65) * 32 * 2;
-        launch("tfdec", 2.0 * B * (NQ * kn + att), [&] { launch_tfdec_mk(t, st); });
+        launch("tfdec", 2.0 * B * (NQ * kn + att), [&] { launch_tfdec_mk(t, st); }, nullptr, -1.0,
+               groups_note(t.groups));
         return;
       }
       launch("misc", 0, [&] { launch_broadcast_rows(W(q_emb), NQ, q, B * NQ, d, st); });

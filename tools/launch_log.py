@@ -58,9 +58,10 @@ def main():
             name, detail, flops, ms = line.rstrip("\n").split("\t")[:4]
             ms = float(ms) / a.reps
             total += ms
-            if not detail:
+            if not detail.startswith("M="):  # no GEMM shape (the megakernels carry only their groups= / form= note)
                 other[name] += ms
                 continue
+            detail = " ".join(t for t in detail.split() if not t.startswith(("cfg=", "form=")))  # group by shape
             g = groups.setdefault(f"{name} {detail}", [0, 0.0, 0.0])
             g[0] += 1
             g[1] += float(flops) / a.reps
