@@ -4,8 +4,9 @@
 // compacted into full 256-row tiles.
 //
 // Two kernels. The union-staged form (vproj_union_kernel, below: the default) stages each tile's union of 3 x 3
-// neighbourhoods in LDS once per channel group. The gathered form here (vproj_kernel<2>) computes the tiles whose
-// union does not fit (fb_only, right after the union launch) and every tile under DDMI_VPROJ_UNION=0.
+// neighbourhoods in LDS once per channel group. The gathered form here computes every tile under DDMI_VPROJ_UNION=0
+// (vproj_kernel<2>) and, right after the union launch, the tiles whose union does not fit (fb_only,
+// vproj_kernel<2, true>: the same gather in the union form's K order and split sums, bit-equal to it).
 //
 // Gathered form, per workgroup: 8 waves (4 x 2, wave tile 64 x 64), a row tile's 128-channel half (the two halves
 // are two workgroups on one XCD); A = the tile's gathered rows by LDS-DMA (per-lane 16-B buffer loads at each row's
@@ -90,12 +91,28 @@ __device__ inline void vp_split8(const float4& p, const float4& q, vp_h8& hi, vp
   }
 }
 
+// a product / a sum rounded on its own, never contracted into an fma with its neighbour: the union-staged kernel
+// rounds its scaled accumulators before the bias (or the other splits' partials) is added
+__device__ inline float vp_mul_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x * y;
+}
+__device__ inline float vp_add_rn(float x, float y) {
+#pragma clang fp contract(off)
+  return x + y;
+}
+
 // cache-policy bits of the raw buffer intrinsics: sc1 (write-through stores, L1-bypassing loads)
 constexpr int kSC1 = 16;
 
 }  // namespace
 
-template <int VP_TN>
+// UORD (the fb_only launch behind the union-staged kernel): the union-staged form's arithmetic, so that a value row
+// does not depend on which of the two kernels computed its tile (a scene's rows land in other tiles, next to other
+// scenes' rows, when its place in the batch changes). K walks (channel group g) x (tap t) in steps of k = 16 - every
+// 32-channel chunk is fetched twice, once per 16-channel half - and with a.usplit = S > 1 the groups' S runs are
+// summed from zero each, scaled, and added in split order, as the union kernel's partials are.
+template <int VP_TN, bool UORD = false>
 __global__ __launch_bounds__(VP_NT) void vproj_kernel(VprojArgs a) {
   constexpr int VP_BN = VpTile<VP_TN>::BN, VP_BB = VpTile<VP_TN>::BB, VP_STAGE = VpTile<VP_TN>::STAGE;
   constexpr int VP_B_IN = VpTile<VP_TN>::B_IN;
@@ -127,7 +144,8 @@ __global__ __launch_bounds__(VP_NT) void vproj_kernel(VprojArgs a) {
   if (mt >= tiles) return;  // workgroup-uniform
   const int m0 = mt * VP_BM;
   const int n0 = nh * VP_BN;
-  constexpr int kbeg = 0, kend = VP_NK;
+  constexpr int NQ = UORD ? 2 * VP_NK : VP_NK;  // K steps: chunks, or (group pair, half, tap) in the union's order
+  auto ck_of = [](int q) { return UORD ? (q % 9) * 8 + q / 18 : q; };
   for (int r = tid; r < VP_BM; r += VP_NT) {
     const int g = m0 + r;
     int idx = -1;
@@ -225,22 +243,35 @@ __global__ __launch_bounds__(VP_NT) void vproj_kernel(VprojArgs a) {
 
   // every chunk issues the same DMA count per wave (out-of-range taps read zero through the offset, not skipped)
   constexpr int DPC = VP_A_IN + 2 * VP_B_IN;
-  issue(0, kbeg);
-  if (NST == 3 && kbeg + 1 < kend) issue(1, kbeg + 1);
+  float sc[VP_TN], bias[VP_TN];
+#pragma unroll
+  for (int j = 0; j < VP_TN; ++j) {
+    const int col = n0 + (wn * VP_TN + j) * 32 + li;
+    sc[j] = a.wsinv[col];
+    bias[j] = a.bias[col];
+  }
+  bool bad = false;
+  // UORD with S > 1: the sum of the scaled runs so far (the union kernel's partials, added in split order)
+  vp_f16 tot[UORD ? VP_TM : 1][UORD ? VP_TN : 1];
+  const int S = UORD ? a.usplit : 1, gper = 16 / S;
+  issue(0, ck_of(0));
+  if (NST == 3 && 1 < NQ) issue(1, ck_of(1));
   int cur = 0;
-  for (int kc = kbeg; kc < kend; ++kc) {
+  for (int kc = 0; kc < NQ; ++kc) {
     // this wave's chunk kc has landed (the younger chunk kc + 1 may stay in flight), every wave's has (barrier),
     // and every wave finished reading chunk kc - 1, whose stage is refilled below
-    if (NST == 3 && kc + 1 < kend)
+    if (NST == 3 && kc + 1 < NQ)
       vp_barrier_n<DPC>();
     else
       vp_barrier0();
     const int nxt = kc + NST - 1;
-    if (nxt < kend) issue(cur == 0 ? NST - 1 : cur - 1, nxt);
+    if (nxt < NQ) issue(cur == 0 ? NST - 1 : cur - 1, ck_of(nxt));
+    const int half = (kc % 18) / 9;  // UORD: the 16-channel half of the chunk this step multiplies
     const char* st = lds + cur * VP_STAGE;
     cur = cur + 1 == NST ? 0 : cur + 1;
 #pragma unroll
     for (int s2 = 0; s2 < 2; ++s2) {
+      if (UORD && s2 != half) continue;  // workgroup-uniform
       vp_h8 ah[VP_TM], al[VP_TM], bh[VP_TN], bl[VP_TN];
 #pragma unroll
       for (int j = 0; j < VP_TN; ++j) {
@@ -267,32 +298,51 @@ __global__ __launch_bounds__(VP_NT) void vproj_kernel(VprojArgs a) {
         for (int j = 0; j < VP_TN; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
     }
+    if constexpr (UORD) {
+      // the last tap of channel group kc / 9: at the end of a split's run, its scaled sum joins the total
+      if (S > 1 && kc % 9 == 8 && (kc / 9 + 1) % gper == 0) {
+        const bool first = kc / 9 + 1 == gper;
+#pragma unroll
+        for (int i = 0; i < VP_TM; ++i)
+#pragma unroll
+          for (int j = 0; j < VP_TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              bad |= !__builtin_isfinite(acc[i][j][r]);
+              const float p = vp_mul_rn(acc[i][j][r], sc[j]);
+              tot[i][j][r] = first ? p : vp_add_rn(tot[i][j][r], p);
+              acc[i][j][r] = 0.f;
+            }
+      }
+    }
   }
 
   // ---- epilogue from the accumulators: element (i, j, r) is row (wm TM + i) 32 + (r & 3) + 8 (r >> 2) + 4 hh of the
   // tile, channel (wn TN + j) 32 + li
-  bool bad = false;
-  float sc[VP_TN], bias[VP_TN];
+  if (UORD && S > 1) {
 #pragma unroll
-  for (int j = 0; j < VP_TN; ++j) {
-    const int col = n0 + (wn * VP_TN + j) * 32 + li;
-    sc[j] = a.wsinv[col];
-    bias[j] = a.bias[col];
+    for (int i = 0; i < VP_TM; ++i)
+#pragma unroll
+      for (int j = 0; j < VP_TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = tot[UORD ? i : 0][UORD ? j : 0][r];
+  } else {
+#pragma unroll
+    for (int i = 0; i < VP_TM; ++i)
+#pragma unroll
+      for (int j = 0; j < VP_TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          bad |= !__builtin_isfinite(acc[i][j][r]);
+          acc[i][j][r] = UORD ? vp_mul_rn(acc[i][j][r], sc[j]) : acc[i][j][r] * sc[j];
+        }
   }
-#pragma unroll
-  for (int i = 0; i < VP_TM; ++i)
-#pragma unroll
-    for (int j = 0; j < VP_TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        bad |= !__builtin_isfinite(acc[i][j][r]);
-        acc[i][j][r] *= sc[j];
-      }
   if (bad && a.flags) atomicOr(a.flags, (unsigned)DD_NUM_F16_OVERFLOW);
   auto row_of = [&](int i, int r) { return (wm * VP_TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh; };
   auto finish = [&](int i, int j, int r, float v) {
     const int ri = g_rows[row_of(i, r)];
-    if (ri >= 0) a.out[(int64_t)ri * kC + n0 + (wn * VP_TN + j) * 32 + li] = fmaxf(v + bias[j], 0.f);
+    const float o = UORD ? vp_add_rn(v, bias[j]) : v + bias[j];
+    if (ri >= 0) a.out[(int64_t)ri * kC + n0 + (wn * VP_TN + j) * 32 + li] = fmaxf(o, 0.f);
   };
 #pragma unroll
   for (int i = 0; i < VP_TM; ++i)
@@ -899,8 +949,8 @@ void launch_vproj(const VprojArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(vproj_union_kernel<true>, dim3((unsigned)(t8 * 2 * a.usplit)), dim3(VU_NT), 0, st, a);
     DD_HIP_CHECK(hipGetLastError());
     VprojArgs f = a;
-    f.fb_only = 1;  // tiles whose union did not fit: the gathered form
-    hipLaunchKernelGGL(vproj_kernel<2>, dim3((unsigned)(t8 * 2)), dim3(VP_NT), 0, st, f);
+    f.fb_only = 1;  // tiles whose union did not fit: the gathered form, in the union form's arithmetic
+    hipLaunchKernelGGL((vproj_kernel<2, true>), dim3((unsigned)(t8 * 2)), dim3(VP_NT), 0, st, f);
   } else {
     hipLaunchKernelGGL(vproj_kernel<2>, dim3((unsigned)(t8 * 2)), dim3(VP_NT), 0, st, a);
   }

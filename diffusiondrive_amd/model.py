@@ -270,6 +270,10 @@ class DiffusionDriveModel:
             timesteps = torch.randint(0, cfg.train_timestep_max, (B,))
         if noise is None:
             noise = torch.randn((B, Q, P, 2))
+        # before anything is staged or launched (a device tensor of timesteps is read back for this)
+        tt = torch.as_tensor(timesteps)
+        if tt.numel() and (int(tt.min()) < 0 or int(tt.max()) >= cfg.num_train_timesteps):
+            raise ValueError(f"timesteps must lie in [0, {cfg.num_train_timesteps})")
         if not safe:
             return self._forward_train(features, targets, timesteps, noise, heads, stream)
         self.numerics_flags(clear=True)
@@ -301,8 +305,6 @@ class DiffusionDriveModel:
             tt = self._dev(timesteps, dtype=torch.int32)
             if tuple(nz.shape) != (B, Q, P, 2) or tuple(tt.shape) != (B,):
                 raise ValueError(f"noise must be (B,{Q},{P},2) and timesteps (B,), got {tuple(nz.shape)}, {tuple(tt.shape)}")
-            if int(tt.min()) < 0 or int(tt.max()) >= cfg.num_train_timesteps:
-                raise ValueError(f"timesteps must lie in [0, {cfg.num_train_timesteps})")
             tg = None
             if targets is not None and targets.get("trajectory") is not None:
                 tg = self._dev(targets["trajectory"])

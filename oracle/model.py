@@ -321,17 +321,17 @@ def trajectory_head_train(ego_q, agents_q, bev, sd, cfg, noise, timesteps, taps=
     embedding (:537-556). Returns (best_reg, [reg per layer], [cls per layer])."""
     p = "_trajectory_head"
     B = ego_q.shape[0]
-    sched = DDIM(cfg.num_train_timesteps)
+    sched = DDIM(cfg.num_train_timesteps, dtype=noise.dtype)
     anchor = sd[p + ".plan_anchor"].unsqueeze(0).repeat(B, 1, 1, 1)
     t = torch.as_tensor(timesteps).to(torch.int64)
     a = sched.ac[t].view(B, 1, 1, 1)
     noisy = a ** 0.5 * norm_odo(anchor) + (1 - a) ** 0.5 * noise
-    pts = denorm_odo(torch.clamp(noisy.float(), -1, 1))
+    pts = denorm_odo(torch.clamp(noisy, -1, 1))
     emb = sine_embed(pts, 64).flatten(-2)
     tf = linear(emb, sd, p + ".plan_anchor_encoder.0")
     tf = layer_norm(F.relu(tf), sd, p + ".plan_anchor_encoder.2")
     tf = linear(tf, sd, p + ".plan_anchor_encoder.3")
-    te = timestep_embed(t)
+    te = timestep_embed(t, dtype=noise.dtype)
     te = linear(mish(linear(te, sd, p + ".time_mlp.1")), sd, p + ".time_mlp.3").view(B, 1, -1)
     values = [F.relu(conv(bev, sd, f"{p}.diff_decoder.layers.{l}.cross_bev_attention.value_proj.0", 1, 1, bias=True))
               for l in range(cfg.num_diff_layers)]

@@ -616,3 +616,89 @@ def test_bevproj_fused(gpu, B):
     ok(gpu.dd_op_bevproj(cd.data_ptr() + 256 * 4, 320, kd.data_ptr(), wd.data_ptr(), bd.data_ptr(), gd.data_ptr(),
                          ld.data_ptr(), out.data_ptr(), B, H, W, 8, 8, None), gpu)
     close(out, ref, 3e-5)
+
+
+# --------------------------------------------------------------------------- dd_bev_semantic_loss (train_loss.hip)
+# test_train_loss.LOSS_TOL["bev_semantic_loss"], relative to max(1, |ref|): per pixel a sum of C exponentials, then a tree
+# sum of non-negative terms (256 per block, the blocks' partials in index order)
+BEV_LOSS_TOL = 1e-5
+BEV_LOSS_SHAPES = [
+    (1, 7, 5, 13, 1.0),      # less than one block
+    (3, 7, 9, 29, 1.0),      # 4 blocks, a tail of 15 pixels, block boundaries inside a scene
+    (2, 1, 4, 8, 1.0),       # C = 1: the loss is exactly 0
+    (1, 255, 3, 5, 1.0),     # the largest C; targets include id 254
+    (1, 7, 260, 256, 1.0),   # 260 partials: the final sum's loop runs twice
+    (3, 7, 9, 29, 30.0),     # the max-subtraction at |logit| ~ 100
+]
+
+
+def _bev_loss(lib, logits_d, target_d, B, C, H, W):
+    """One dd_bev_semantic_loss call on device tensors with the scratch filled with NaN: the loss as a 0-d tensor."""
+    n = int(lib.dd_bev_semantic_loss_work(B, H, W))
+    assert n == -(-B * H * W // 256)
+    work = torch.full((n,), float("nan"), device=DEV)
+    loss = torch.full((1,), float("nan"), device=DEV)
+    ok(lib.dd_bev_semantic_loss(logits_d.data_ptr(), target_d.data_ptr(), B, C, H, W, work.data_ptr(), loss.data_ptr(),
+                                None), lib)
+    return loss[0].cpu()
+
+
+@pytest.mark.parametrize("B,C,H,W,scale", BEV_LOSS_SHAPES)
+def test_bev_semantic_loss(gpu, B, C, H, W, scale):
+    """bev_ce_partial_kernel + sum_partials_kernel through the C ABI vs F.cross_entropy in float64 on the same logits
+    and ids; the scratch starts as NaN (every partial the final sum reads must have been written), two calls return
+    the same bits."""
+    logits = rnd(B, C, H, W, seed=111, scale=3.0 * scale)
+    gen = torch.Generator().manual_seed(112)
+    target = torch.randint(0, C, (B, H, W), generator=gen).to(torch.uint8)
+    if C == 255:
+        target[0, 0, 0], target[0, -1, -1] = 254, 0
+        assert int(target.max()) == 254
+    if scale > 1:
+        assert float(logits.abs().max()) > 100.0
+    ref = float(F.cross_entropy(logits.double(), target.long()))
+    ld, td = g(logits), g(target)
+    a = _bev_loss(gpu, ld, td, B, C, H, W)
+    b = _bev_loss(gpu, ld, td, B, C, H, W)
+    assert a.view(torch.int32) == b.view(torch.int32), (float(a), float(b))
+    if C == 1:
+        assert ref == 0.0 and float(a) == 0.0
+    err = abs(float(a) - ref)
+    print(f"bev_semantic_loss {(B, C, H, W)} x{scale:g}: ref {ref:.9g} err {err:.3e}")
+    assert err <= BEV_LOSS_TOL * max(1.0, abs(ref)), (float(a), ref)
+
+
+def test_bev_semantic_loss_poisons_an_id_outside_the_classes(gpu):
+    """One pixel with id == C (F.cross_entropy raises on it): the loss is NaN, as the kernel documents, in the block of
+    that pixel's scene and whichever block it is in; without it the loss is finite."""
+    B, C, H, W = 3, 7, 9, 29
+    logits = rnd(B, C, H, W, seed=113)
+    target = torch.randint(0, C, (B, H, W), generator=torch.Generator().manual_seed(114)).to(torch.uint8)
+    ld = g(logits)
+    assert torch.isfinite(_bev_loss(gpu, ld, g(target), B, C, H, W))
+    for where in ((0, 0, 0), (1, 4, 17), (2, 8, 28)):
+        bad = target.clone()
+        bad[where] = C
+        bd = g(bad)
+        assert torch.isnan(_bev_loss(gpu, ld, bd, B, C, H, W)), where
+
+
+def test_bev_semantic_loss_rejects_bad_arguments(gpu):
+    """C = 0, C = 256 and a null pointer: DD_ERR_INVALID with a message in dd_op_last_error, nothing launched."""
+    B, H, W = 1, 4, 8
+    ld, td = g(rnd(B, 7, H, W, seed=115)), g(torch.zeros(B, H, W, dtype=torch.uint8))
+    work, loss = torch.zeros(1, device=DEV), torch.full((1,), 5.0, device=DEV)
+    ptrs = [ld.data_ptr(), td.data_ptr(), work.data_ptr(), loss.data_ptr()]
+
+    def call(p, C):
+        return gpu.dd_bev_semantic_loss(p[0], p[1], B, C, H, W, p[2], p[3], None)
+
+    cases = [(ptrs, 0), (ptrs, 256)] + [(ptrs[:i] + [None] + ptrs[i + 1:], 7) for i in range(4)]
+    for p, C in cases:
+        assert call(p, C) == -1, (p, C)  # DD_ERR_INVALID (include/ddmi.h)
+        assert b"dd_bev_semantic_loss" in gpu.dd_op_last_error()
+    torch.cuda.synchronize()
+    assert float(loss) == 5.0
+    assert call(ptrs, 7) == 0
+    torch.cuda.synchronize()
+    assert np.isfinite(float(loss))
