@@ -285,8 +285,8 @@ class Model {
   float* train_loss_dev = nullptr;      // [3] trajectory_loss_0, _1, sum
 
   Model(const dd_config& c, const void* blob, size_t bytes, int dev) : cfg(c), device(dev) {
+    BlobIndex bx(blob, bytes);  // host only: a blob that does not parse is refused before any device call
     DD_HIP_CHECK(hipSetDevice(device));
-    BlobIndex bx(blob, bytes);
     build(bx);
     ar.upload();
     decoder_init_constants();
@@ -2370,13 +2370,34 @@ void dd_default_config(dd_config* c) {
 
 const char* dd_last_error(void) { return g_last_error.c_str(); }
 
+// The configurations the kernels compute correctly (include/ddmi.h, dd_config; DESIGN.md §5, "Configuration
+// matrix"): everything else is refused here, before the blob is parsed and before any device call. Each message
+// names its field.
+static void validate_config(const dd_config& c) {
+  auto bad = [](const char* field, int v, const char* want) {
+    throw std::invalid_argument(std::string("dd_create: ") + field + " = " + std::to_string(v) + " is not supported (" +
+                                want + ")");
+  };
+  if (c.abi_version != DD_ABI_VERSION) throw std::invalid_argument("dd_create: ABI version mismatch");
+  if (c.cam_h != 256 || c.cam_w != 1024 || c.lidar_h != 256 || c.lidar_w != 256)
+    throw std::invalid_argument("dd_create: only the reference resolutions (256x1024 camera, 256x256 LiDAR) are supported");
+  if (c.image_arch != 34 && c.image_arch != 50) bad("image_arch", c.image_arch, "34 or 50");
+  // _bev_downscale, the keyval strides and the BEV-feature tap are written for the 512-channel layer-4 map
+  if (c.lidar_arch != 34) bad("lidar_arch", c.lidar_arch, "34: the BEV tokens read a 512-channel LiDAR layer-4 map");
+  if (c.lidar_channels < 1 || c.lidar_channels > 4) bad("lidar_channels", c.lidar_channels, "1..4");
+  // plan_anchor_encoder.0 is 512 = 8 x 64 wide and the decoder's logits buffer holds 8 columns per row
+  if (c.num_poses != 8) bad("num_poses", c.num_poses, "8: the anchor encoder is 8 x 64 wide");
+  // select_mode / the loss read mode 0 unconditionally; traj_loss_scene's LDS arrays hold DD_MAX_MODES entries
+  if (c.num_modes < 1 || c.num_modes > DD_MAX_MODES) bad("num_modes", c.num_modes, "1..128");
+  // both index the 1000-entry alphas_cumprod table (trunc_timestep directly, step_span as the bound of the roll)
+  if (c.trunc_timestep < 0 || c.trunc_timestep > 999) bad("trunc_timestep", c.trunc_timestep, "0..999");
+  if (c.step_span < 1 || c.step_span > 1000) bad("step_span", c.step_span, "1..1000");
+}
+
 int dd_create(const dd_config* cfg, const void* blob, size_t bytes, int device, dd_handle** out) {
   return guarded([&] {
     if (!cfg || !blob || !out) throw std::invalid_argument("dd_create: null argument");
-    if (cfg->abi_version != DD_ABI_VERSION) throw std::invalid_argument("dd_create: ABI version mismatch");
-    if (cfg->cam_h != 256 || cfg->cam_w != 1024 || cfg->lidar_h != 256 || cfg->lidar_w != 256)
-      throw std::invalid_argument("dd_create: only the reference resolutions (256x1024 camera, 256x256 LiDAR) are supported");
-    if (cfg->num_modes > 128 || cfg->num_poses > 16) throw std::invalid_argument("dd_create: too many modes/poses");
+    validate_config(*cfg);
     auto h = std::make_unique<dd_handle>();
     h->m = std::make_unique<Model>(*cfg, blob, bytes, device);
     *out = h.release();

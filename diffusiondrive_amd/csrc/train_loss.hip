@@ -78,23 +78,28 @@ __global__ void timestep_embed_rows_kernel(const int* __restrict__ t, float* out
 
 // LossComputer per scene (multimodal_loss.py:131-168): mode = argmin_m mean_p ||target_p[:2] - anchor_{m,p}||;
 // part[b] = (sum_m focal(cls[b, m], onehot(mode)), sum_{p,c} |reg[b, mode, p, c] - target[b, p, c]|)
+// One workgroup of 64 threads per scene; thread t takes modes t, t + 64, ... (Q <= kLossModes, the LDS arrays' size;
+// launch_traj_loss_scene refuses more). Every per-mode term goes to LDS and thread 0 reduces in mode order 0, 1, ...,
+// Q - 1 (the argmin's first minimum, the focal sum): the order does not depend on how the modes fell to the threads,
+// so Q <= 64 computes what the one-mode-per-thread form computed, to the bit.
+constexpr int kLossModes = 128;
 __global__ __launch_bounds__(64) void traj_loss_scene_kernel(const float* __restrict__ reg, const float* __restrict__ cls,
                                                              const float* __restrict__ target,
                                                              const float* __restrict__ anchor, float* part, int Q,
                                                              int P, float alpha, float gamma) {
   const int b = blockIdx.x, lane = threadIdx.x;
-  __shared__ float dist[64];
+  __shared__ float dist[kLossModes];
   __shared__ int mode_s;
-  __shared__ float foc[64];
+  __shared__ float foc[kLossModes];
   const float* tg = target + (int64_t)b * P * 3;
-  if (lane < Q) {
+  for (int q = lane; q < Q; q += 64) {
     float s = 0.f;
     for (int p = 0; p < P; ++p) {
-      const float dx = tg[p * 3 + 0] - anchor[(lane * P + p) * 2 + 0];
-      const float dy = tg[p * 3 + 1] - anchor[(lane * P + p) * 2 + 1];
+      const float dx = tg[p * 3 + 0] - anchor[(q * P + p) * 2 + 0];
+      const float dy = tg[p * 3 + 1] - anchor[(q * P + p) * 2 + 1];
       s = s + sqrtf(dx * dx + dy * dy);
     }
-    dist[lane] = s / (float)P;
+    dist[q] = s / (float)P;
   }
   __syncthreads();
   if (lane == 0) {
@@ -105,16 +110,14 @@ __global__ __launch_bounds__(64) void traj_loss_scene_kernel(const float* __rest
   }
   __syncthreads();
   const int mode = mode_s;
-  float f = 0.f;
-  if (lane < Q) {
-    const float x = cls[(int64_t)b * Q + lane];
-    const float t = lane == mode ? 1.f : 0.f;
+  for (int q = lane; q < Q; q += 64) {
+    const float x = cls[(int64_t)b * Q + q];
+    const float t = q == mode ? 1.f : 0.f;
     const float ps = 1.f / (1.f + expf(-x));
     const float pt = (1.f - ps) * t + ps * (1.f - t);
     const float fw = (alpha * t + (1.f - alpha) * (1.f - t)) * (gamma == 2.f ? pt * pt : powf(pt, gamma));
-    f = bce_logits(x, t) * fw;
+    foc[q] = bce_logits(x, t) * fw;
   }
-  foc[lane] = f;
   __syncthreads();
   if (lane == 0) {
     float fs = 0.f, ls = 0.f;
@@ -205,7 +208,7 @@ void launch_timestep_embed_rows(const int* t, float* out, int B, int dim, hipStr
 
 void launch_traj_loss_scene(const float* reg, const float* cls, const float* target, const float* anchor, float* part,
                             int B, int Q, int P, hipStream_t st) {
-  if (Q > 64) throw std::runtime_error("traj_loss: Q > 64");
+  if (Q < 1 || Q > kLossModes) throw std::invalid_argument("traj_loss: num_modes must be in [1, 128]");
   hipLaunchKernelGGL(traj_loss_scene_kernel, dim3(B), dim3(64), 0, st, reg, cls, target, anchor, part, Q, P, 0.25f,
                      2.0f);
   DD_HIP_CHECK(hipGetLastError());

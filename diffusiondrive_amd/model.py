@@ -22,14 +22,22 @@ from .schema import state_dict_schema
 from .weights import pack_blob, strip_prefix
 
 ARCH_CODE = {"resnet34": 34, "resnet50": 50}
+LIDAR_ARCH_CODE = {"resnet34": 34}  # dd_create: the BEV tokens read a 512-channel LiDAR layer-4 map
 
 
 def make_dd_config(cfg: TransfuserConfig) -> _lib.DDConfig:
+    """The dd_config of ``cfg``. The values dd_create refuses for a reason the config alone shows (include/ddmi.h)
+    raise ValueError here, before the library is loaded."""
+    if cfg.image_architecture not in ARCH_CODE:
+        raise ValueError(f"image_architecture must be one of {sorted(ARCH_CODE)}, got {cfg.image_architecture!r}")
+    if cfg.lidar_architecture not in LIDAR_ARCH_CODE:
+        raise ValueError(f"lidar_architecture must be 'resnet34' (the only LiDAR trunk the forward supports), "
+                         f"got {cfg.lidar_architecture!r}")
     c = _lib.DDConfig()
     lib = _lib.load()
     lib.dd_default_config(c)
     c.image_arch = ARCH_CODE[cfg.image_architecture]
-    c.lidar_arch = ARCH_CODE[cfg.lidar_architecture]
+    c.lidar_arch = LIDAR_ARCH_CODE[cfg.lidar_architecture]
     c.cam_h, c.cam_w = cfg.camera_height, cfg.camera_width
     c.lidar_h, c.lidar_w = cfg.lidar_resolution_height, cfg.lidar_resolution_width
     c.lidar_channels = cfg.lidar_in_channels

@@ -128,6 +128,10 @@ def state_dict_schema(cfg: TransfuserConfig) -> List[Entry]:
     _linear(out, "_agent_head._mlp_label.0", 1, d)
 
     npose = cfg.trajectory_sampling.num_poses
+    if npose != 8:
+        # plan_anchor_encoder.0 reads the 8 poses' 64-wide sine embeddings (512 inputs, transfuser_model_v2.py:455):
+        # the reference builds no model for another pose count, and neither does dd_create
+        raise ValueError(f"num_poses must be 8 (plan_anchor_encoder.0 is 8 x 64 wide), got {npose}")
     p = "_trajectory_head"
     out.append((f"{p}.plan_anchor", (cfg.num_modes, npose, 2), "anchor"))
     _linear(out, f"{p}.plan_anchor_encoder.0", d, 512)

@@ -37,18 +37,24 @@ extern "C" {
 
 typedef struct dd_handle dd_handle;
 
-/* Mirrors the TransfuserConfig fields the hot path reads (transfuser_config.py:10-149). */
+#define DD_MAX_MODES 128    /* largest dd_config.num_modes */
+
+/* Mirrors the TransfuserConfig fields the hot path reads (transfuser_config.py:10-149). Each field lists its default
+ * and the values dd_create accepts; any other value returns DD_ERR_INVALID with the field's name in dd_last_error(),
+ * before the weight blob is parsed and before any device call. Every accepted value is held to the float64 oracle
+ * (tests/test_config_matrix_gpu.py; DESIGN.md section 5, "Configuration matrix"). */
 typedef struct dd_config {
   int abi_version;     /* DD_ABI_VERSION */
-  int image_arch;      /* 34 = resnet34 (default), 50 = resnet50 (nuScenes-style config C4) */
-  int lidar_arch;      /* 34 */
-  int cam_h, cam_w;    /* 256, 1024 */
-  int lidar_h, lidar_w;/* 256, 256 */
-  int lidar_channels;  /* 1 (use_ground_plane = False) */
-  int num_modes;       /* 20 anchors */
-  int num_poses;       /* 8 */
-  int trunc_timestep;  /* 8  (transfuser_model_v2.py:594) */
-  int step_span;       /* 20 (transfuser_model_v2.py:585) */
+  int image_arch;      /* 34 = resnet34 (default), 50 = resnet50 (nuScenes-style config C4); nothing else */
+  int lidar_arch;      /* 34 only (the BEV tokens read a 512-channel LiDAR layer-4 map) */
+  int cam_h, cam_w;    /* 256, 1024 only */
+  int lidar_h, lidar_w;/* 256, 256 only */
+  int lidar_channels;  /* 1 (use_ground_plane = False); 1..4 = lidar_seq_len x (2 if use_ground_plane else 1) */
+  int num_modes;       /* 20 anchors; 1..DD_MAX_MODES (20 runs the decoder megakernel, any other count the unfused
+                          chain of the same layers) */
+  int num_poses;       /* 8 only (plan_anchor_encoder.0 is 8 x 64 wide) */
+  int trunc_timestep;  /* 8  (transfuser_model_v2.py:594); 0..999, an index into the 1000 alphas_cumprod */
+  int step_span;       /* 20 (transfuser_model_v2.py:585); 1..1000, and a truncated forward takes steps <= step_span */
 } dd_config;
 
 /* Optional outputs of dd_forward_ex (device pointers; NULL = not requested). */
