@@ -45,6 +45,16 @@ class DDTrainOutputs(ctypes.Structure):
     ]
 
 
+class DDSampleOutputs(ctypes.Structure):
+    _fields_ = [
+        ("trajectory", c_void_p), ("poses_reg", c_void_p), ("poses_cls", c_void_p),
+        ("best_trajectory", c_void_p), ("best_index", c_void_p),
+        ("bev_semantic_map", c_void_p), ("agent_states", c_void_p), ("agent_labels", c_void_p),
+    ]
+
+
+MAX_SAMPLES = 32  # DD_MAX_SAMPLES
+
 # name -> (restype, argtypes)
 _SIGS = {
     "dd_default_config": (None, [ctypes.POINTER(DDConfig)]),
@@ -54,6 +64,8 @@ _SIGS = {
                                   c_void_p, c_void_p, c_void_p, c_void_p]),
     "dd_forward_ex": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
                                      ctypes.c_int, ctypes.POINTER(DDOutputs), c_void_p]),
+    "dd_forward_samples": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDSampleOutputs), c_void_p]),
     "dd_destroy": (ctypes.c_int, [c_void_p]),
     "dd_last_error": (ctypes.c_char_p, []),
     "dd_set_profiling": (ctypes.c_int, [c_void_p, ctypes.c_int]),

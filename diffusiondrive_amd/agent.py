@@ -151,9 +151,27 @@ class DiffusionDriveAgent(_Base):
         from .losses import transfuser_loss
         return transfuser_loss(targets, predictions, self._config, self._transfuser_model)
 
-    def forward_trajectory(self, features, noise=None, steps=None) -> Dict[str, torch.Tensor]:
-        """Trajectory-only fast path (no BEV-semantic / agent heads)."""
-        return self._transfuser_model.forward(features, noise=noise, steps=steps)
+    def forward_trajectory(self, features, noise=None, steps=None, num_samples: int = 1) -> Dict[str, torch.Tensor]:
+        """Trajectory-only fast path (no BEV-semantic / agent heads). ``num_samples`` > 1: that many draws per scene
+        over one perception pass (``DiffusionDriveModel.forward_samples``; ``trajectory`` (B, S, P, 3), ``noise``
+        (B, S, Q, P, 2)); 1 (default) is the plain forward."""
+        if num_samples == 1:
+            return self._transfuser_model.forward(features, noise=noise, steps=steps)
+        return self._transfuser_model.forward_samples(features, num_samples, noise=noise, steps=steps)
+
+    def compute_trajectories(self, agent_input, num_samples: int) -> List[Trajectory]:
+        """``num_samples`` draws of the planner's trajectory distribution for one scene (best-of-N under an external
+        scorer, mode diversity): ``compute_trajectory``'s feature building, one perception pass, one Trajectory per
+        start noise. No reference counterpart (abstract_agent.py:65-86 draws one)."""
+        self.eval()
+        features: Dict[str, torch.Tensor] = {}
+        for builder in self.get_feature_builders():
+            features.update(builder.compute_features(agent_input))
+        features = {k: v.unsqueeze(0) for k, v in features.items()}
+        with torch.no_grad():
+            poses = self._transfuser_model.forward_samples(features, num_samples)["trajectory"][0].cpu().numpy()
+        cls = _NavsimTrajectory if HAVE_NAVSIM else Trajectory
+        return [cls(p) for p in poses]
 
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).

@@ -84,6 +84,9 @@ struct ConvArgs {
   // rowmap_nimg = images in the input (operand-extent check).
   const int* rowmap = nullptr;
   int rowmap_nimg = 0;
+  // row groups of the compacted form below (0: rowmap_nimg, one group per image; dd_forward_samples runs several
+  // decoder scenes - groups - over one image)
+  int rowmap_groups = 0;
   // Compacted gathered rows: rowcount[n] live rows of image n sit at rowmap[n * rowcap + l], l < rowcount[n];
   // launch row m is the m-th live row over the images in order (rows past the total are don't-care), and
   // its output goes to row n * rowcap + l - so every tile is full except the last, and the output layout
@@ -322,7 +325,8 @@ struct VprojArgs {
   const float* bias = nullptr;
   const int* rows = nullptr;
   const int* counts = nullptr;
-  int B = 0, cap = 0;
+  int B = 0, cap = 0;     // row groups (counts[B], cap rows each): one per decoder scene
+  int nimg = 0;           // images in `map` (0: B, one per row group); rows[] name pixels of images [0, nimg)
   float* part = nullptr;  // the union form's split partials (usplit > 1): [usplit][B * cap][256]
   float* out = nullptr;
   unsigned* flags = nullptr;
@@ -419,24 +423,27 @@ void launch_timestep_embed(float t, float* out, int dim, hipStream_t st);
 // value (NHWC, Hv x Wv x C, zero padding, align_corners=False) at P points, weighted sum -> out[C].
 void launch_bev_sample_attn(const float* logits, const float* pts, const float* value, float* out,
                             int B, int Q, int P, int Hv, int Wv, int C, float inv_max_x,
-                            float inv_max_y, hipStream_t st);
+                            float inv_max_y, hipStream_t st, int samples = 1);
+// (samples, here and below: consecutive groups of `samples` decoder scenes read one perception scene's map - scene
+// b takes value map / map image b / samples, B counts decoder scenes; dd_forward_samples)
 // Gathered form (decoder.hip): the (B*Q*P*4) tap pixels (or -1) of the points, and the sampling
 // attention over a compact (B*Q*P*4, C) value array holding the conv at those taps.
 void launch_bev_tap_rows(const float* pts, int* rows, int B, int Q, int P, int Hv, int Wv, float inv_max_x,
-                         float inv_max_y, hipStream_t st);
+                         float inv_max_y, hipStream_t st, int samples = 1);
 // Deduplicated taps (one workgroup per scene, Hv * Wv <= 4096, else false and nothing launched):
 // rows[b * Q*P*4 + j] = the scene's j-th distinct tap pixel (pixel order; -1 past its count),
 // slots[tap] = the compact row holding the tap's pixel (-1 for zero padding).
 bool launch_bev_tap_dedup(const float* pts, int* rows, int* slots, int B, int Q, int P, int Hv, int Wv,
-                          float inv_max_x, float inv_max_y, hipStream_t st);
+                          float inv_max_x, float inv_max_y, hipStream_t st, int samples = 1);
 // slots == nullptr: row of tap t of point ip is ip * 4 + t (launch_bev_tap_rows layout)
 void launch_bev_sample_attn_gathered(const float* logits, const float* pts, const float* vrows, const int* slots,
                                      float* out, int B, int Q, int P, int Hv, int Wv, int C, float inv_max_x,
                                      float inv_max_y, hipStream_t st);
 // Small multi-head attention: out[b,i,h*hd+d] = sum_j softmax_j(q.k / sqrt(hd)) v. Lk <= 128, hd <= 64.
+// Query batch b attends to K / V batch b / kv_div (kv_div query batches share one K / V batch).
 void launch_mha_small(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv,
                       float* out, int64_t ldo, int B, int Lq, int Lk, int nh, int hd,
-                      int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, hipStream_t st);
+                      int64_t q_bstride, int64_t kv_bstride, int64_t o_bstride, hipStream_t st, int kv_div = 1);
 // reg (rows, P, 3) from the raw branch output r (rows, P*3): xy += pts, heading = tanh * pi;
 // optionally also writes the cascade's next points (rows, P, 2).
 void launch_reg_finalize(const float* r, const float* pts, float* reg, float* pts_next, int rows, int P,
@@ -446,6 +453,10 @@ void launch_ddim_step(const float* reg, float* img, int rows, int P, float a_t, 
                       hipStream_t st);
 // argmax over Q cls logits per scene, gather reg[b, argmax] -> traj (B, P, 3); also writes index.
 void launch_select_mode(const float* cls, const float* reg, float* traj, int* idx, int B, int Q, int P,
+                        hipStream_t st);
+// Best candidate of each scene over its N = S x Q candidates (cls [B][N], reg [B][N][P][3]): idx[b] = the first
+// maximal cls index, traj[b] = that candidate's poses (B, P, 3); either output may be nullptr.
+void launch_select_best(const float* cls, const float* reg, float* traj, int* idx, int B, int N, int P,
                         hipStream_t st);
 // Agent head post-processing: states (rows, 5) in place: [0:2] = tanh*32, [2] = tanh*pi.
 void launch_agent_post(float* states, int rows, hipStream_t st);

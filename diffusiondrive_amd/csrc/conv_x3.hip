@@ -102,8 +102,9 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvArgs a, int M
   const int n0 = nt_idx * BN;
   if constexpr (GATHER) {
     if (a.rowcount) {
-      // exclusive prefix of the images' live-row counts; launch row m = the m-th live row in image order
-      const int nimg = a.rowmap_nimg;
+      // exclusive prefix of the row groups' live-row counts (one group per image unless rowmap_groups says
+      // otherwise); launch row m = the m-th live row in group order
+      const int nimg = a.rowmap_groups > 0 ? a.rowmap_groups : a.rowmap_nimg;
       rowcount_prefix(a.rowcount, nimg, g_pre);
       const int total = g_pre[nimg];
       if (m0 >= total) return;  // past every live row (workgroup-uniform)
@@ -633,8 +634,10 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t st) {
   if (a.rowmap && (a.stride != 1 || a.Cin % BK != 0 || a.KH * a.KW > 32 || a.Nimg != 1 || a.Wo != 1 ||
                    a.rowmap_nimg < 1 || a.prec != 0))
     throw std::runtime_error("conv_x3: gathered rows need a stride-1 f16x3 MODE-1 conv into Nimg=1, Wo=1");
-  if (a.rowcount && (!a.rowmap || a.rowmap_nimg > 256 || a.rowcap < 1 || (int64_t)a.rowmap_nimg * a.rowcap > M))
-    throw std::runtime_error("conv_x3: compacted rows need a row map of <= 256 images x rowcap rows");
+  const int row_groups = a.rowmap_groups > 0 ? a.rowmap_groups : a.rowmap_nimg;
+  if (a.rowcount && (!a.rowmap || row_groups > 256 || a.rowmap_nimg > row_groups || a.rowcap < 1 ||
+                     (int64_t)row_groups * a.rowcap > M))
+    throw std::runtime_error("conv_x3: compacted rows need a row map of <= 256 groups x rowcap rows");
   const int64_t in_extent = (int64_t)((a.rowmap ? a.rowmap_nimg : a.Nimg) - 1) * a.in_sn + (int64_t)(a.H - 1) * a.in_sh +
                             (int64_t)(a.W - 1) * a.in_sw + a.Cin;
   if (in_extent * 4 >= (int64_t)kOOB || (int64_t)a.Cout * a.ldh * 2 >= (int64_t)kOOB)

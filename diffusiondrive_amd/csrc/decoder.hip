@@ -98,11 +98,12 @@ __global__ __launch_bounds__(256) void bev_sample_attn_kernel(const float* __res
                                                               const float* __restrict__ pts,
                                                               const float* __restrict__ value,
                                                               float* __restrict__ out, int B, int Q, int P, int Hv,
-                                                              int Wv, int C, float inv_max_x, float inv_max_y) {
+                                                              int Wv, int C, float inv_max_x, float inv_max_y,
+                                                              int samples) {
   const int lane = threadIdx.x & 63;
   const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (item >= B * Q) return;
-  const int b = item / Q;
+  const int b = item / Q / samples;  // the value map of the decoder scene's perception scene
   const float* lg = logits + (int64_t)item * P;
   float mx = -INFINITY;
   for (int p = 0; p < P; ++p) mx = fmaxf(mx, lg[p]);
@@ -155,11 +156,13 @@ __global__ __launch_bounds__(256) void bev_sample_attn_kernel(const float* __res
 }
 
 void launch_bev_sample_attn(const float* logits, const float* pts, const float* value, float* out, int B, int Q,
-                            int P, int Hv, int Wv, int C, float inv_max_x, float inv_max_y, hipStream_t st) {
+                            int P, int Hv, int Wv, int C, float inv_max_x, float inv_max_y, hipStream_t st,
+                            int samples) {
   if (P > 16 || C % 4) throw std::runtime_error("bev_sample_attn: P <= 16 and C % 4 == 0 required");
+  if (samples < 1 || B % samples) throw std::runtime_error("bev_sample_attn: B must be a multiple of samples");
   const int items = B * Q;
   hipLaunchKernelGGL(bev_sample_attn_kernel, dim3((items + 3) / 4), dim3(256), 0, st, logits, pts, value, out, B, Q,
-                     P, Hv, Wv, C, inv_max_x, inv_max_y);
+                     P, Hv, Wv, C, inv_max_x, inv_max_y, samples);
   DD_HIP_CHECK(hipGetLastError());
 }
 
@@ -190,10 +193,10 @@ __device__ inline void bev_tap_geometry(const float* pts, int64_t ip, int Hv, in
 
 __global__ __launch_bounds__(256) void bev_tap_rows_kernel(const float* __restrict__ pts, int* __restrict__ rows,
                                                            int B, int Q, int P, int Hv, int Wv, float inv_max_x,
-                                                           float inv_max_y) {
+                                                           float inv_max_y, int samples) {
   const int64_t ip = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (ip >= (int64_t)B * Q * P) return;
-  const int b = (int)(ip / ((int64_t)Q * P));
+  const int b = (int)(ip / ((int64_t)Q * P)) / samples;  // the map image of the decoder scene
   int x0, y0;
   float wt[4];
   bev_tap_geometry(pts, ip, Hv, Wv, inv_max_x, inv_max_y, x0, y0, wt);
@@ -214,7 +217,7 @@ __global__ __launch_bounds__(256) void bev_tap_rows_kernel(const float* __restri
 // offsets) and writes each tap's compact row (or -1 for a zero-padded tap) to slots.
 __global__ __launch_bounds__(256) void bev_tap_dedup_kernel(const float* __restrict__ pts, int* __restrict__ rows,
                                                             int* __restrict__ slots, int Q, int P, int Hv, int Wv,
-                                                            float inv_max_x, float inv_max_y) {
+                                                            float inv_max_x, float inv_max_y, int samples) {
   __shared__ int table[4096];
   __shared__ int scan[256];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -250,7 +253,7 @@ __global__ __launch_bounds__(256) void bev_tap_dedup_kernel(const float* __restr
   for (int e = tid * E; e < min(HW, tid * E + E); ++e)
     if (table[e]) {
       table[e] = r;
-      rows[base + r] = b * HW + e;
+      rows[base + r] = (b / samples) * HW + e;  // the map image; the row base stays the decoder scene's
       ++r;
     }
   for (int j = total + tid; j < cap; j += 256) rows[base + j] = -1;
@@ -320,22 +323,24 @@ __global__ __launch_bounds__(256) void bev_sample_attn_gathered_kernel(
 }
 
 void launch_bev_tap_rows(const float* pts, int* rows, int B, int Q, int P, int Hv, int Wv, float inv_max_x,
-                         float inv_max_y, hipStream_t st) {
+                         float inv_max_y, hipStream_t st, int samples) {
   const int64_t n = (int64_t)B * Q * P;
   if (n == 0) return;
+  if (samples < 1 || B % samples) throw std::runtime_error("bev_tap_rows: B must be a multiple of samples");
   if ((int64_t)B * Hv * Wv >= (int64_t(1) << 31)) throw std::runtime_error("bev_tap_rows: map too large");
   hipLaunchKernelGGL(bev_tap_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, pts, rows, B, Q, P,
-                     Hv, Wv, inv_max_x, inv_max_y);
+                     Hv, Wv, inv_max_x, inv_max_y, samples);
   DD_HIP_CHECK(hipGetLastError());
 }
 
 bool launch_bev_tap_dedup(const float* pts, int* rows, int* slots, int B, int Q, int P, int Hv, int Wv,
-                          float inv_max_x, float inv_max_y, hipStream_t st) {
+                          float inv_max_x, float inv_max_y, hipStream_t st, int samples) {
+  if (samples < 1 || B % samples) throw std::runtime_error("bev_tap_dedup: B must be a multiple of samples");
   if (Hv * Wv > 4096 || (int64_t)B * Q * P * 4 >= (int64_t(1) << 31) || (int64_t)B * Hv * Wv >= (int64_t(1) << 31))
     return false;
   if (B == 0) return true;
   hipLaunchKernelGGL(bev_tap_dedup_kernel, dim3(B), dim3(256), 0, st, pts, rows, slots, Q, P, Hv, Wv, inv_max_x,
-                     inv_max_y);
+                     inv_max_y, samples);
   DD_HIP_CHECK(hipGetLastError());
   return true;
 }
@@ -358,7 +363,7 @@ __global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict_
                                                         const float* __restrict__ k, const float* __restrict__ v,
                                                         int64_t ldkv, float* __restrict__ out, int64_t ldo, int B,
                                                         int Lq, int Lk, int nh, int hd, int64_t qbs, int64_t kvbs,
-                                                        int64_t obs) {
+                                                        int64_t obs, int kv_div) {
   __shared__ float pbuf[4][128];
   const int lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6;
@@ -369,8 +374,8 @@ __global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict_
   const int h = (it / Lq) % nh;
   const int b = it / (Lq * nh);
   const float* qr = q + b * qbs + (int64_t)i * ldq + h * hd;
-  const float* kb = k + b * kvbs + h * hd;
-  const float* vb = v + b * kvbs + h * hd;
+  const float* kb = k + (b / kv_div) * kvbs + h * hd;
+  const float* vb = v + (b / kv_div) * kvbs + h * hd;
   const float scale = 1.0f / sqrtf((float)hd);
   float s0 = -INFINITY, s1 = -INFINITY;
   if (lane < Lk) {
@@ -416,7 +421,8 @@ __global__ __launch_bounds__(256) void mha_small_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void mha_head_kernel(const float* __restrict__ q, int64_t ldq,
                                                        const float* __restrict__ k, const float* __restrict__ v,
                                                        int64_t ldkv, float* __restrict__ out, int64_t ldo, int Lq,
-                                                       int Lk, int nh, int hd, int64_t qbs, int64_t kvbs, int64_t obs) {
+                                                       int Lk, int nh, int hd, int64_t qbs, int64_t kvbs, int64_t obs,
+                                                       int kv_div) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int hp = hd + 1;  // padded row pitch (conflict-free column walks)
   float* Qs = sm;                  // [Lq][hp]
@@ -426,8 +432,8 @@ __global__ __launch_bounds__(256) void mha_head_kernel(const float* __restrict__
   const int pp = Lk + 1;
   const int h = blockIdx.x % nh, b = blockIdx.x / nh;
   const float* qb = q + b * qbs + h * hd;
-  const float* kb = k + b * kvbs + h * hd;
-  const float* vb = v + b * kvbs + h * hd;
+  const float* kb = k + (b / kv_div) * kvbs + h * hd;  // kv_div query batches share one K / V batch
+  const float* vb = v + (b / kv_div) * kvbs + h * hd;
   for (int t = threadIdx.x; t < Lq * hd; t += 256) {
     const int i = t / hd, e = t - i * hd;
     Qs[i * hp + e] = qb[(int64_t)i * ldq + e];
@@ -476,20 +482,21 @@ __global__ __launch_bounds__(256) void mha_head_kernel(const float* __restrict__
 
 void launch_mha_small(const float* q, int64_t ldq, const float* k, const float* v, int64_t ldkv, float* out,
                       int64_t ldo, int B, int Lq, int Lk, int nh, int hd, int64_t q_bstride, int64_t kv_bstride,
-                      int64_t o_bstride, hipStream_t st) {
+                      int64_t o_bstride, hipStream_t st, int kv_div) {
   if (Lk > 128 || Lk < 1) throw std::runtime_error("mha_small: 1 <= Lk <= 128 required");
+  if (kv_div < 1 || B % kv_div) throw std::runtime_error("mha_small: B must be a multiple of kv_div");
   const size_t lds = sizeof(float) * ((size_t)Lq * (hd + 1) + (size_t)Lk * (hd + 1) + (size_t)Lk * hd +
                                       (size_t)Lq * (Lk + 1));
   if (lds <= 64 * 1024) {
     hipLaunchKernelGGL(mha_head_kernel, dim3(B * nh), dim3(256), lds, st, q, ldq, k, v, ldkv, out, ldo, Lq, Lk, nh,
-                       hd, q_bstride, kv_bstride, o_bstride);
+                       hd, q_bstride, kv_bstride, o_bstride, kv_div);
     DD_HIP_CHECK(hipGetLastError());
     return;
   }
   const int items = B * nh * Lq;
 
   hipLaunchKernelGGL(mha_small_kernel, dim3((items + 3) / 4), dim3(256), 0, st, q, ldq, k, v, ldkv, out, ldo, B, Lq,
-                     Lk, nh, hd, q_bstride, kv_bstride, o_bstride);
+                     Lk, nh, hd, q_bstride, kv_bstride, o_bstride, kv_div);
   DD_HIP_CHECK(hipGetLastError());
 }
 
@@ -570,6 +577,52 @@ __global__ void select_mode_kernel(const float* __restrict__ cls, const float* _
 void launch_select_mode(const float* cls, const float* reg, float* traj, int* idx, int B, int Q, int P,
                         hipStream_t st) {
   hipLaunchKernelGGL(select_mode_kernel, dim3(blocks_for(B, 64)), dim3(64), 0, st, cls, reg, traj, idx, B, Q, P);
+  DD_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- best candidate over a scene's samples
+// One wave per scene: the candidate with the largest cls logit over the scene's S x Q candidates (cls [B][S*Q], reg
+// [B][S*Q][P][3]); first maximal index s * Q + q, NaN first like select_mode_kernel's torch.argmax rule.
+__global__ __launch_bounds__(64) void select_best_kernel(const float* __restrict__ cls, const float* __restrict__ reg,
+                                                         float* __restrict__ traj, int* __restrict__ idx, int N,
+                                                         int P) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* c = cls + (int64_t)b * N;
+  // per lane: the first maximum (or first NaN) of its strided candidates, in index order
+  int best = -1;
+  float bv = 0.f;
+  for (int i = lane; i < N; i += 64) {
+    const float v = c[i];
+    if (best < 0 || v > bv || (v != v && bv == bv)) {
+      bv = v;
+      best = i;
+    }
+  }
+  // a beats b: a NaN over a number, else the larger value, ties (and two NaNs) to the smaller index
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(best, o, 64);
+    if (oi < 0) continue;
+    const bool on = ov != ov, mn = bv != bv;
+    const bool take = best < 0 || (on != mn ? on : ((on || ov == bv) ? oi < best : ov > bv));
+    if (take) {
+      bv = ov;
+      best = oi;
+    }
+  }
+  if (idx && lane == 0) idx[b] = best;
+  if (traj) {
+    const float* src = reg + ((int64_t)b * N + best) * P * 3;
+    for (int e = lane; e < P * 3; e += 64) traj[(int64_t)b * P * 3 + e] = src[e];
+  }
+}
+
+void launch_select_best(const float* cls, const float* reg, float* traj, int* idx, int B, int N, int P,
+                        hipStream_t st) {
+  if (B <= 0) return;
+  if (N < 1) throw std::runtime_error("select_best: at least one candidate per scene");
+  hipLaunchKernelGGL(select_best_kernel, dim3(B), dim3(64), 0, st, cls, reg, traj, idx, N, P);
   DD_HIP_CHECK(hipGetLastError());
 }
 

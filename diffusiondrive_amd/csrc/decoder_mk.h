@@ -42,7 +42,10 @@ struct MkArgs {
   MkLayer L;
   MkAnchor A;
   int layer = 0;        // 0: embed + anchor encoder first; 1: DDIM step / mode selection last
-  int B = 0;
+  int B = 0;            // decoder scenes (one workgroup set each)
+  // samples per perception scene: decoder scene b reads akv / ego of scene b / samples and writes image b / samples
+  // into the next tap table (dd_forward_samples); every other per-scene operand is per decoder scene
+  int samples = 1;
   // layer 0: DDIM sample in, this step's points / traj_feature out; layer 1: traj_feature and the
   // layer-0 points in
   float* imgx = nullptr;          // [B][Q][P][2]
@@ -51,8 +54,8 @@ struct MkArgs {
   float* pts_next = nullptr;      // [B*Q*P][2] layer 0: its reg xy (layer 1's points)
   const float* vrows = nullptr;   // gathered value rows of this (step, layer)
   const int* slots = nullptr;     // [B][Q*P*4] compact row of each tap, -1 = zero padding
-  const float* akv = nullptr;     // [B][30][512] agent K | V
-  const float* ego = nullptr;     // [B][256] hoisted ego attention output
+  const float* akv = nullptr;     // [B / samples][30][512] agent K | V
+  const float* ego = nullptr;     // [B / samples][256] hoisted ego attention output
   const float* film = nullptr;    // [512] FiLM scale | shift of this (step, layer), or [B][512] (film_stride 512)
   int film_stride = 0;            // floats between scenes' FiLM vectors (0: one for the batch)
   float* gs_out = nullptr;        // [B*Q][256] BEV attention aggregate (tap)
@@ -88,6 +91,7 @@ struct MkInitArgs {
   const float* sa_b = nullptr;   // per-scene add_noise coefficients (training head, forward_train), or nullptr
   const float* s1a_b = nullptr;
   int B = 0;
+  int samples = 1;  // decoder scenes per map image: scene b's rows name image b / samples
 };
 
 // Returns false (nothing launched) unless Q = 20 queries, P = 8 points, d = 256, 8 heads, 30 agents, a

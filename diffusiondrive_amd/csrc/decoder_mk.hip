@@ -86,8 +86,10 @@ __device__ inline void tap_geom(float tx, float ty, int& x0, int& y0, float wt[4
 
 // the scene's distinct tap pixels (pixel order) -> rows[b*cap ..], -1 past the count, the count -> counts[b]
 // (the gathered value_proj compacts the scenes' rows with it); each tap's compact row -> slots
-// (bev_tap_dedup_kernel's algorithm with the workgroup's threads)
-__device__ void dedup_scene(const float* pts, int* table, int* scan, int b, int* rows, int* slots, int* counts) {
+// (bev_tap_dedup_kernel's algorithm with the workgroup's threads). img = the map image the scene samples (its
+// perception scene: b / samples); counts, slots and the compact row base stay per decoder scene b
+__device__ void dedup_scene(const float* pts, int* table, int* scan, int b, int img, int* rows, int* slots,
+                            int* counts) {
   const int tid = threadIdx.x, nt = blockDim.x;
   constexpr int HW = kHV * kHV, cap = kQP * 4;
   const int64_t base = (int64_t)b * cap;
@@ -129,7 +131,7 @@ __device__ void dedup_scene(const float* pts, int* table, int* scan, int b, int*
   for (int e = tid * E; e < min(HW, tid * E + E); ++e)
     if (table[e]) {
       table[e] = r;
-      rows[base + r] = b * HW + e;
+      rows[base + r] = img * HW + e;
       ++r;
     }
   for (int j = total + tid; j < cap; j += nt) rows[base + j] = -1;
@@ -178,6 +180,7 @@ __global__ __launch_bounds__(NT, 1) void decoder_mk_kernel(MkArgs a) {
   float* SM = reinterpret_cast<float*>(lds + OFF_SMALL);
   const float* __restrict__ dim_t = a.dim_t;
   const int b = blockIdx.x / G, gi = blockIdx.x % G, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int bp = b / a.samples;   // the perception scene (map image, agent K / V, ego row) of decoder scene b
   const int q0 = gi * QG;         // first query of the group in the scene
   const int row0 = b * kQ + q0;   // its global query row
   const int64_t pt0 = (int64_t)b * kQP + q0 * kP;  // its first (query, point) of the scene's
@@ -382,7 +385,7 @@ __global__ __launch_bounds__(NT, 1) void decoder_mk_kernel(MkArgs a) {
   stamp(8);
   float* KV = reinterpret_cast<float*>(SA);
   {
-    const float4* src = reinterpret_cast<const float4*>(a.akv + (int64_t)b * kA * 2 * kD);
+    const float4* src = reinterpret_cast<const float4*>(a.akv + (int64_t)bp * kA * 2 * kD);
     for (int e = tid; e < kA * 2 * kD / 4; e += NT) reinterpret_cast<float4*>(KV)[e] = src[e];
   }
   __syncthreads();
@@ -467,7 +470,7 @@ __global__ __launch_bounds__(NT, 1) void decoder_mk_kernel(MkArgs a) {
   stamp(14);
   // norm1; cross_ego_attention over one key = the hoisted ego row, residual; norm2 -> FFN operand
   {
-    const float4 eg = reinterpret_cast<const float4*>(a.ego + (int64_t)b * kD)[lane];
+    const float4 eg = reinterpret_cast<const float4*>(a.ego + (int64_t)bp * kD)[lane];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int q = wave + 8 * k;
@@ -714,7 +717,7 @@ __global__ __launch_bounds__(NT, 1) void decoder_mk_kernel(MkArgs a) {
   }
   if (a.next_rows) {
     int* table = reinterpret_cast<int*>(T1);
-    dedup_scene(SM + S_PN, table, table + 4096, b, a.next_rows, a.next_slots, a.next_counts);
+    dedup_scene(SM + S_PN, table, table + 4096, b, bp, a.next_rows, a.next_slots, a.next_counts);
   }
 #ifdef DDMI_MK_STAMPS
   stamp(32);
@@ -739,7 +742,7 @@ __global__ __launch_bounds__(256) void decoder_mk_init_kernel(MkInitArgs a) {
     pts[2 * t + 1] = denorm_y(fminf(fmaxf(iy, -1.f), 1.f));
   }
   __syncthreads();
-  dedup_scene(pts, table, table + 4096, b, a.rows, a.slots, a.counts);
+  dedup_scene(pts, table, table + 4096, b, b / a.samples, a.rows, a.slots, a.counts);
 }
 
 // GEMM-core test: A [32][K] fp32 -> split LDS image -> mk_gemm over 256-column units -> out
@@ -831,6 +834,7 @@ bool decoder_mk_supported(int Q, int P, int d, int nagents, int Hv, int Wv, int 
 
 void launch_decoder_mk(const MkArgs& a, hipStream_t st) {
   if (a.B <= 0) return;
+  if (a.samples < 1 || a.B % a.samples) throw std::runtime_error("decoder_mk: B must be a multiple of samples");
   if (!a.dim_t || !a.slots || !a.vrows || !a.akv || !a.ego || !a.film || !a.tfe || !a.pts || !a.imgx)
     throw std::runtime_error("decoder_mk: missing operand");
   if (a.groups != 1 && (!a.scene_cnt || !a.cls_x || (a.layer == 1 && a.ddim && !a.next_pts) ||
@@ -852,6 +856,7 @@ void launch_decoder_mk(const MkArgs& a, hipStream_t st) {
 
 void launch_decoder_mk_init(const MkInitArgs& a, hipStream_t st) {
   if (a.B <= 0) return;
+  if (a.samples < 1 || a.B % a.samples) throw std::runtime_error("decoder_mk_init: B must be a multiple of samples");
   hipLaunchKernelGGL(decoder_mk_init_kernel, dim3(a.B), dim3(256), 0, st, a);
   DD_HIP_CHECK(hipGetLastError());
 }

@@ -270,7 +270,8 @@ class Model {
   // buffer offsets stay below 2 GiB up to 256 scenes; DDMI_MAX_CHUNK overrides, read at dd_create)
   int max_chunk = 128;
   // noise == NULL: the DDIM start noise is drawn on the device (Philox4x32-10 + Box-Muller, keyed by
-  // rng_seed; scene s of the stream since dd_set_seed takes draws [s Q P 2, (s + 1) Q P 2))
+  // rng_seed; draw block k of the stream since dd_set_seed takes draws [k Q P 2, (k + 1) Q P 2): one block per scene
+  // of a forward, one per (scene, sample) of a samples forward). rng_next = the next block
   uint64_t rng_seed = 0, rng_next = 0;
   // dd_forward_train (the training-mode trajectory head as a loss evaluator, TrajectoryHead.forward_train
   // transfuser_model_v2.py:520-576): set for the duration of one such call. The head then runs ONE pass of the two
@@ -283,6 +284,11 @@ class Model {
   float* train_part = nullptr;          // [2 layers][B][2] LossComputer partials of the whole call
   size_t train_part_n = 0;
   float* train_loss_dev = nullptr;      // [3] trajectory_loss_0, _1, sum
+  // dd_forward_samples: set for the duration of one such call. Every scene of a chunk then runs `samples` decoder
+  // scenes (one per start noise) over its one perception pass: decoder scene d = b * samples + s reads the cross-BEV
+  // map, agent K / V and ego row of scene d / samples; everything else in the trajectory head is per decoder scene.
+  int samples = 1;
+  bool want_best = false;  // also pick each scene's best candidate over its samples x Q (best_trajectory / best_index)
 
   Model(const dd_config& c, const void* blob, size_t bytes, int dev) : cfg(c), device(dev) {
     BlobIndex bx(blob, bytes);  // host only: a blob that does not parse is refused before any device call
@@ -688,16 +694,19 @@ class Model {
   // 128-row tiles; without counts one tile run per scene). Timed under its own class "value_proj";
   // its FLOPs count every row slot (2 x slots x 256 x 2304; bench.py derives the live-row rate from the counts).
   // busy_cus: CUs a kernel on the other branch holds meanwhile (the tf-decoder megakernel: one per scene)
-  void gathered_value(int l, const int* rows, const int* counts, float* vrows, const float* cross, int B, int HB,
-                      int WB, int MR, int busy_cus = 0) {
+  // B counts the row groups (decoder scenes), nimg the images of `cross` their rows name (B / samples): every
+  // operand-extent check describes the nimg real images
+  void gathered_value(int l, const int* rows, const int* counts, float* vrows, const float* cross, int B, int nimg,
+                      int HB, int WB, int MR, int busy_cus = 0) {
     const int d = 256;
-    ConvArgs a = conv_args(dl[l].vproj, cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, B, HB, WB, vrows,
+    ConvArgs a = conv_args(dl[l].vproj, cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, nimg, HB, WB, vrows,
                            (int64_t)MR * d, d, 0, true, nullptr, 0, 0, 0);
     a.Nimg = 1;
     a.Ho = MR;
     a.Wo = 1;
     a.rowmap = rows;
-    a.rowmap_nimg = B;
+    a.rowmap_nimg = nimg;
+    a.rowmap_groups = B;
     if (counts) {
       a.rowcount = counts;
       a.rowcap = MR / B;
@@ -716,6 +725,7 @@ class Model {
       v.rows = rows;
       v.counts = counts;
       v.B = B;
+      v.nimg = nimg;
       v.cap = MR / B;
       v.out = vrows;
       v.flags = num_flags;
@@ -752,8 +762,9 @@ class Model {
 
   // TrajectoryHead.forward_test (:578-641) as 1 + 2 x steps x 2 launches: the DDIM start + first taps, then
   // per (step, layer) the gathered value_proj conv and the decoder megakernel (decoder_mk.hip)
-  void traj_head_mk(int B, int steps, const float* cross, float* const akv[2], float* const egos[2],
-                    bool& tf_pending, const float* noise) {
+  // B = decoder scenes of this head pass, S samples each of B / S perception scenes (cross, akv, egos are theirs)
+  void traj_head_mk(int B, int S, int steps, const float* cross, float* const akv[2], float* const egos[2],
+                    bool& tf_pending, int tf_scenes, const float* noise) {
     const int d = 256, Q = cfg.num_modes, P = cfg.num_poses, R = B * Q;
     const int HB = cfg.lidar_h / 4, WB = cfg.lidar_w / 4, MR = R * P * 4;
     const bool vanilla = schedule == DD_SCHED_VANILLA;
@@ -787,6 +798,7 @@ class Model {
         ia.s1a_b = bufs.at("train_s1a").first;
       }
       ia.B = B;
+      ia.samples = S;
       launch("decoder", 0, [&] { launch_decoder_mk_init(ia, st); });
       // the packed decoder weights (~8.6 MB) into the MALL before the first layer streams them from HBM
       launch("misc", 0, [&] {
@@ -805,7 +817,8 @@ class Model {
       for (int l = 0; l < 2; ++l) {
         const std::string sf = sfx(si, l);
         float* vrows = buf("value_rows" + sf, (size_t)MR * d);
-        gathered_value(l, rows_of(si, l), counts_of(si, l), vrows, cross, B, HB, WB, MR, tf_pending ? B : 0);
+        gathered_value(l, rows_of(si, l), counts_of(si, l), vrows, cross, B, B / S, HB, WB, MR,
+                       tf_pending ? tf_scenes : 0);
         if (tf_pending) {
           join();  // tf decoder: agent K / V and ego rows of both layers
           tf_pending = false;
@@ -815,6 +828,7 @@ class Model {
         m.A = anc;
         m.layer = l;
         m.B = B;
+        m.samples = S;
         m.imgx = imgx;
         m.tfe = tfe;
         m.pts = l == 0 ? pts : pts2;
@@ -1561,6 +1575,9 @@ class Model {
     float* reg_l[2] = {nullptr, nullptr};
     float* cls_l[2] = {nullptr, nullptr};
     float* part_l[2] = {nullptr, nullptr};
+    // forward_samples: the scene's best candidate over its S x Q
+    float* best_traj = nullptr;
+    int* best_idx = nullptr;
   };
 
   // denoise timesteps. truncated: roll_timesteps = round(arange(steps) * step_span / steps)[::-1]
@@ -1852,7 +1869,6 @@ class Model {
     // value_proj for both decoder layers (main stream, beside the tf decoder), then join. (Layer 1's
     // on a third stream beside the first trajectory-head layer was measured: the graph put it on
     // the hardware queue of layer 0's and the head behind it - no overlap.)
-    const int R = B * Q;  // trajectory query rows
     // In f16x3 mode the conv is instead evaluated per (step, layer) at the B x Q x P x 4 bilinear taps
     // grid_sample reads (gathered rows, below): 40960 rows per call at B = 64 instead of 262144 per layer.
     const bool gathered = gemm_mode == DD_GEMM_F16X3 && dl[0].vproj.x3.hi != kNone &&
@@ -1896,11 +1912,73 @@ class Model {
       }
     });
 
-    // ---- trajectory head (TrajectoryHead.forward_test, :578-641)
-    if (decoder_mk && mk_ready && gathered) {
-      traj_head_mk(B, steps, cross, akv, egos, tf_pending, noise);
-      return;
+    // ---- trajectory head (TrajectoryHead.forward_test, :578-641). With samples = S > 1 (dd_forward_samples) every
+    // scene runs S decoder scenes over its one perception result, decoder scene d = b * S + s; the head takes the
+    // chunk's scenes in consecutive ranges of at most max_chunk / S, all S samples of a range in one pass, so that
+    // no pass sees more than max_chunk decoder scenes. The named buffers keep the last pass; with several passes
+    // each pass's results are gathered into "samples_*" (kernel launches: the captured forward has no copy nodes).
+    const int S = samples, npass = head_passes(B), per = (B + npass - 1) / npass;
+    float* all_traj = nullptr;
+    float* all_reg = nullptr;
+    float* all_cls = nullptr;
+    if (npass > 1) {
+      all_traj = buf("samples_trajectory", (size_t)B * S * P * 3);
+      all_reg = buf("samples_reg", (size_t)B * S * Q * P * 3);
+      all_cls = buf("samples_cls", (size_t)B * S * Q);
     }
+    const std::string last_sfx = "_s" + std::to_string(steps - 1) + "l1";
+    for (int b0 = 0; b0 < B; b0 += per) {
+      const int nb = std::min(per, B - b0), D = nb * S;
+      const float* cross_p = cross + (size_t)b0 * HB * WB * d;
+      const float* noise_p = noise + (size_t)b0 * S * Q * P * 2;
+      float* akv_p[2];
+      float* egos_p[2];
+      float* vals_p[2];
+      for (int l = 0; l < 2; ++l) {
+        akv_p[l] = akv[l] + (size_t)b0 * 30 * 2 * d;
+        egos_p[l] = egos[l] + (size_t)b0 * d;
+        vals_p[l] = vals[l] ? vals[l] + (size_t)b0 * HB * WB * d : nullptr;
+      }
+      if (decoder_mk && mk_ready && gathered)
+        traj_head_mk(D, S, steps, cross_p, akv_p, egos_p, tf_pending, B, noise_p);
+      else
+        traj_head_chain(D, S, steps, cross_p, akv_p, egos_p, vals_p, gathered, tf_pending, noise_p);
+      if (npass > 1) {
+        const size_t d0 = (size_t)b0 * S;
+        launch("misc", 0, [&] {
+          launch_broadcast_rows(bufs.at("trajectory").first, D, all_traj + d0 * P * 3, D, P * 3, st);
+        });
+        launch("misc", 0, [&] {
+          launch_broadcast_rows(bufs.at("reg" + last_sfx).first, D * Q, all_reg + d0 * Q * P * 3, D * Q, P * 3, st);
+        });
+        launch("misc", 0, [&] {
+          launch_broadcast_rows(bufs.at("cls" + last_sfx).first, D, all_cls + d0 * Q, D, Q, st);
+        });
+      }
+    }
+    if (want_best) {
+      // the scene's best candidate over its S x Q: one launch after the last head pass
+      const float* cls_all = npass > 1 ? all_cls : bufs.at("cls" + last_sfx).first;
+      const float* reg_all = npass > 1 ? all_reg : bufs.at("reg" + last_sfx).first;
+      float* bt = buf("best_trajectory", (size_t)B * P * 3);
+      int* bi = reinterpret_cast<int*>(buf("best_index", B));
+      launch("select_best", 0, [&] { launch_select_best(cls_all, reg_all, bt, bi, B, S * Q, P, st); });
+    }
+  }
+
+  // head passes of a chunk of B scenes at the current samples count (1 unless B * samples exceeds max_chunk)
+  int head_passes(int B) const {
+    const int per_max = std::max(1, max_chunk / samples);
+    return (B + per_max - 1) / per_max;
+  }
+
+  // The unfused trajectory head (every config the megakernel is not specialised for, the fp32 mode, DDMI_DECODER_MK=0):
+  // D = decoder scenes of this pass, S samples each of D / S perception scenes, whose cross map, value maps (dense
+  // form), agent K / V and ego rows the pointers name
+  void traj_head_chain(int D, int S, int steps, const float* cross, float* const akv[2], float* const egos[2],
+                       float* const vals[2], bool gathered, bool& tf_pending, const float* noise) {
+    const int d = 256, Q = cfg.num_modes, P = cfg.num_poses, R = D * Q;
+    const int HB = cfg.lidar_h / 4, WB = cfg.lidar_w / 4;
     float* imgx = buf("ddim_img", (size_t)R * P * 2);
     const bool vanilla = schedule == DD_SCHED_VANILLA;
     {
@@ -1910,11 +1988,11 @@ class Model {
       const float sa = vanilla ? 0.0f : std::sqrt(a8), s1a = vanilla ? 1.0f : std::sqrt(1.0f - a8);
       if (train)  // forward_train: per-scene timesteps (train_time_film)
         launch("misc", 0, [&] {
-          launch_train_noisy(W(anchor), noise, bufs.at("train_sa").first, bufs.at("train_s1a").first, imgx, B, Q * P,
+          launch_train_noisy(W(anchor), noise, bufs.at("train_sa").first, bufs.at("train_s1a").first, imgx, D, Q * P,
                              st);
         });
       else
-        launch("misc", 0, [&] { launch_ddim_init(W(anchor), noise, imgx, B, Q * P, sa, s1a, st); });
+        launch("misc", 0, [&] { launch_ddim_init(W(anchor), noise, imgx, D, Q * P, sa, s1a, st); });
     }
     float* pts = buf("pts", (size_t)R * P * 2);
     float* pts2 = buf("pts_next", (size_t)R * P * 2);
@@ -1959,20 +2037,22 @@ class Model {
         bool dd = false;
         if (slots)
           launch("misc", 0, [&] {
-            dd = launch_bev_tap_dedup(pts_l, rows, slots, B, Q, P, HB, WB, 1.0f / 32.0f, 1.0f / 32.0f, st);
+            dd = launch_bev_tap_dedup(pts_l, rows, slots, D, Q, P, HB, WB, 1.0f / 32.0f, 1.0f / 32.0f, st, S);
           });
         if (!dd) {
           slots = nullptr;
-          launch("misc", 0, [&] { launch_bev_tap_rows(pts_l, rows, B, Q, P, HB, WB, 1.0f / 32.0f, 1.0f / 32.0f, st); });
+          launch("misc", 0, [&] {
+            launch_bev_tap_rows(pts_l, rows, D, Q, P, HB, WB, 1.0f / 32.0f, 1.0f / 32.0f, st, S);
+          });
         }
         vslots_l[l] = slots;
-        ConvArgs a = conv_args(dl[l].vproj, cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, B, HB, WB, vrows,
+        ConvArgs a = conv_args(dl[l].vproj, cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, D / S, HB, WB, vrows,
                                (int64_t)MR * d, d, 0, true, nullptr, 0, 0, 0);
         a.Nimg = 1;
         a.Ho = MR;
         a.Wo = 1;
         a.rowmap = rows;
-        a.rowmap_nimg = B;
+        a.rowmap_nimg = D / S;  // the images of `cross`; the rows are the D decoder scenes' taps
         const double fl = 2.0 * MR * (double)d * 9 * dl[l].vproj.cin_real;
         launch("conv_x3", fl, [&] { launch_conv_gemm(a, st); }, &a);
         vrows_l[l] = vrows;
@@ -2006,12 +2086,12 @@ class Model {
           }
           float* vrows = vrows_l[l];
           launch("bev_sample", 0, [&] {
-            launch_bev_sample_attn_gathered(logit, cur, vrows, vslots_l[l], gso, B, Q, P, HB, WB, d, 1.0f / 32.0f,
+            launch_bev_sample_attn_gathered(logit, cur, vrows, vslots_l[l], gso, D, Q, P, HB, WB, d, 1.0f / 32.0f,
                                             1.0f / 32.0f, st);
           });
         } else {
           launch("bev_sample", 0, [&] {
-            launch_bev_sample_attn(logit, cur, vals[l], gso, B, Q, P, HB, WB, d, 1.0f / 32.0f, 1.0f / 32.0f, st);
+            launch_bev_sample_attn(logit, cur, vals[l], gso, D, Q, P, HB, WB, d, 1.0f / 32.0f, 1.0f / 32.0f, st, S);
           });
         }
         gemm(w.outp, gso, d, R, x1, d, false, tfe, d);
@@ -2022,13 +2102,13 @@ class Model {
           tf_pending = false;
         }
         launch("mha", 0, [&] {
-          launch_mha_small(qa, d, akv[l], akv[l] + d, 2 * d, gs, d, B, Q, 30, 8, 32, (int64_t)Q * d,
-                           (int64_t)30 * 2 * d, (int64_t)Q * d, st);
+          launch_mha_small(qa, d, akv[l], akv[l] + d, 2 * d, gs, d, D, Q, 30, 8, 32, (int64_t)Q * d,
+                           (int64_t)30 * 2 * d, (int64_t)Q * d, st, S);
         });
         gemm(w.ag_out, gs, d, R, x2, d, false, x1, d);
         ln(w.n1, x2, d, x2, d, R);
         // cross_ego_attention (hoisted, exact) + norm2
-        ln(w.n2, x2, d, x3, d, R, egos[l], d, Q);
+        ln(w.n2, x2, d, x3, d, R, egos[l], d, Q * S);  // row r: scene r / Q / S
         // ffn -> norm3 -> FiLM time modulation
         gemm(w.ffn0, x3, d, R, hf, 1024, true);
         gemm(w.ffn2, hf, 1024, R, x2, d);
@@ -2064,23 +2144,25 @@ class Model {
         launch("misc", 0, [&] { launch_ddim_step(reg_last, imgx, R, P, a_t, a_p, st); });
       }
     }
-    float* traj = buf("trajectory", (size_t)B * P * 3);
-    int* idx = reinterpret_cast<int*>(buf("mode_idx", B));
+    float* traj = buf("trajectory", (size_t)D * P * 3);
+    int* idx = reinterpret_cast<int*>(buf("mode_idx", D));
     join();  // the cls branches (and the heads branch before them on the side stream)
-    launch("misc", 0, [&] { launch_select_mode(cls_last, reg_last, traj, idx, B, Q, P, st); });
+    launch("misc", 0, [&] { launch_select_mode(cls_last, reg_last, traj, idx, D, Q, P, st); });
     alias("poses_reg", reg_last);
     alias("poses_cls", cls_last);
-    train_loss_partials(B);
+    train_loss_partials(D);
   }
 
   std::map<std::string, float*> aliases;
   void alias(const std::string& name, float* p) { aliases[name] = p; }
 
-  // noise == NULL: draw it on the device for scenes [scene0, scene0 + B) of the handle's stream
+  // noise == NULL: draw it on the device, draw blocks [block0, block0 + B * samples) of the handle's stream (a
+  // block = the Q * P * 2 normals of one decoder scene; sample s of the chunk's scene b takes block0 + b * samples + s)
   void stage_inputs(const float* camera, const float* lidar, const float* status, const float* noise, int B,
-                    uint64_t scene0) {
+                    uint64_t block0) {
     float* st_in = buf("in_status", (size_t)B * 8);
-    const size_t per = (size_t)cfg.num_modes * cfg.num_poses * 2;
+    const size_t blk = (size_t)cfg.num_modes * cfg.num_poses * 2;
+    const size_t per = blk * (size_t)samples;  // noise floats per scene
     float* nz = buf("in_noise", (size_t)B * per);
     if (use_nchw_stem()) {
       // the stems read the caller's NCHW tensors in place: only their addresses go to the device table (the
@@ -2104,7 +2186,7 @@ class Model {
     if (noise)
       DD_HIP_CHECK(hipMemcpyAsync(nz, noise, sizeof(float) * B * per, hipMemcpyDeviceToDevice, st));
     else
-      launch("misc", 0, [&] { launch_normal_philox(nz, (int64_t)(B * per), rng_seed, scene0 * per, st); });
+      launch("misc", 0, [&] { launch_normal_philox(nz, (int64_t)(B * per), rng_seed, block0 * blk, st); });
   }
 
   void copy_out(float* dst, const std::string& name, size_t n) {
@@ -2147,6 +2229,54 @@ class Model {
                     off(noise, (size_t)Q * P * 2), n, steps, oc, caller, rng_next + (uint64_t)b0);
     }
     if (!noise) rng_next += (uint64_t)B;
+  }
+
+  // S trajectory samples per scene over one perception pass (dd_forward_samples): the scene chunks of forward(), the
+  // backbone at the chunk's full batch, the trajectory head over decoder scenes d = b * S + s in passes of at most
+  // max_chunk of them (forward_body). noise (B,S,Q,P,2) or nullptr: draw blocks [rng_next, rng_next + B * S).
+  void forward_samples(const float* camera, const float* lidar, const float* status, const float* noise, int B, int S,
+                       int steps, const Outs& o, hipStream_t caller) {
+    if (S < 1 || S > DD_MAX_SAMPLES)
+      throw std::invalid_argument("dd_forward_samples: S must be in [1, " + std::to_string(DD_MAX_SAMPLES) + "], got " +
+                                  std::to_string(S));
+    if (S > max_chunk)
+      throw std::invalid_argument("dd_forward_samples: S = " + std::to_string(S) + " exceeds the handle's chunk limit " +
+                                  "(max_chunk = " + std::to_string(max_chunk) + " decoder scenes per head pass)");
+    if (B <= 0) throw std::invalid_argument("batch must be positive");
+    if (steps <= 0 || steps > (schedule == DD_SCHED_VANILLA ? 1000 : cfg.step_span))
+      throw std::invalid_argument("steps must be in [1, step_span] (truncated) or [1, 1000] (vanilla)");
+    if (!camera || !lidar || !status || !o.traj) throw std::invalid_argument("null input/output pointer");
+    if (!noise && (cfg.num_modes * cfg.num_poses) % 2)
+      throw std::invalid_argument("device noise draw needs num_modes * num_poses even");
+    struct Reset {
+      Model& m;
+      ~Reset() {
+        m.samples = 1;
+        m.want_best = false;
+      }
+    } reset{*this};
+    samples = S;
+    want_best = o.best_traj || o.best_idx;
+    const int Q = cfg.num_modes, P = cfg.num_poses;
+    const int nch = (B + max_chunk - 1) / max_chunk, chunk = (B + nch - 1) / nch;
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+      const int n = std::min(chunk, B - b0);
+      auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+      auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+      Outs oc;
+      oc.traj = offw(o.traj, (size_t)S * P * 3);
+      oc.modes = offw(o.modes, (size_t)S * Q * P * 3);
+      oc.cls = offw(o.cls, (size_t)S * Q);
+      oc.best_traj = offw(o.best_traj, (size_t)P * 3);
+      oc.best_idx = o.best_idx ? o.best_idx + b0 : nullptr;
+      oc.sem = offw(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
+      oc.ag_states = offw(o.ag_states, (size_t)30 * 5);
+      oc.ag_labels = offw(o.ag_labels, (size_t)30);
+      forward_chunk(off(camera, (size_t)3 * cfg.cam_h * cfg.cam_w),
+                    off(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w), off(status, 8),
+                    off(noise, (size_t)S * Q * P * 2), n, steps, oc, caller, rng_next + (uint64_t)b0 * S);
+    }
+    if (!noise) rng_next += (uint64_t)B * S;
   }
 
   // The training-mode trajectory head (forward_train, transfuser_model_v2.py:520-576) over the eval-mode network, as
@@ -2248,7 +2378,8 @@ class Model {
     if (generation != gen0) known_shapes.clear();
     const std::string key = std::to_string(B) + "/" + std::to_string(steps) + "/" + std::to_string(heads) + "/g" +
                             std::to_string(gemm_mode) + "/s" + std::to_string(schedule) +
-                            (train ? (train_target ? "/train1" : "/train0") : "");
+                            (train ? (train_target ? "/train1" : "/train0") : "") + "/x" + std::to_string(samples) +
+                            (want_best ? "/best" : "");
     if (use_graph && !profiling && known_shapes.count(key)) {
       if (graph_gen != generation || programs.size() > 8) {
         // an earlier replay may still run (on the caller's stream in direct mode): ev_out marks the last forward
@@ -2277,9 +2408,23 @@ class Model {
     }
     const int Q = cfg.num_modes, P = cfg.num_poses;
     DD_TRACE("copy out");
-    copy_out(o.traj, "trajectory", (size_t)B * P * 3);
-    copy_out(o.modes, "poses_reg", (size_t)B * Q * P * 3);
-    copy_out(o.cls, "poses_cls", (size_t)B * Q);
+    if (samples > 1) {
+      // by buffer name (the aliases are the last eager pass's): the last pass's buffers, or the gathered passes
+      const size_t D = (size_t)B * samples;
+      const bool multi = head_passes(B) > 1;
+      const std::string sf = "_s" + std::to_string(steps - 1) + "l1";
+      copy_out(o.traj, multi ? "samples_trajectory" : "trajectory", D * P * 3);
+      copy_out(o.modes, multi ? "samples_reg" : "reg" + sf, D * Q * P * 3);
+      copy_out(o.cls, multi ? "samples_cls" : "cls" + sf, D * Q);
+    } else {
+      copy_out(o.traj, "trajectory", (size_t)B * P * 3);
+      copy_out(o.modes, "poses_reg", (size_t)B * Q * P * 3);
+      copy_out(o.cls, "poses_cls", (size_t)B * Q);
+    }
+    if (want_best) {
+      copy_out(o.best_traj, "best_trajectory", (size_t)B * P * 3);
+      copy_out(reinterpret_cast<float*>(o.best_idx), "best_index", (size_t)B);
+    }
     if (heads) {
       copy_out(o.sem, "bev_semantic_map", (size_t)B * 7 * (cfg.lidar_h / 2) * cfg.lidar_w);
       copy_out(o.ag_states, "agent_states", (size_t)B * 30 * 5);
@@ -2420,6 +2565,24 @@ int dd_forward_ex(dd_handle* h, const float* camera, const float* lidar, const f
     o.ag_states = outs->agent_states;
     o.ag_labels = outs->agent_labels;
     h->m->forward(camera, lidar, status, noise, B, steps, o, static_cast<hipStream_t>(stream));
+  });
+}
+
+int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
+                       int B, int S, int steps, const dd_sample_outputs* outs, void* stream) {
+  return guarded([&] {
+    if (!h || !outs) throw std::invalid_argument("dd_forward_samples: null handle/outputs");
+    std::lock_guard<std::mutex> lk(h->mu);
+    Model::Outs o;
+    o.traj = outs->trajectory;
+    o.modes = outs->poses_reg;
+    o.cls = outs->poses_cls;
+    o.best_traj = outs->best_trajectory;
+    o.best_idx = outs->best_index;
+    o.sem = outs->bev_semantic_map;
+    o.ag_states = outs->agent_states;
+    o.ag_labels = outs->agent_labels;
+    h->m->forward_samples(camera, lidar, status, noise, B, S, steps, o, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -2618,7 +2781,7 @@ int dd_set_seed_at(dd_handle* h, unsigned long long seed, unsigned long long fir
     if (!h) throw std::invalid_argument("null handle");
     std::lock_guard<std::mutex> lk(h->mu);
     h->m->rng_seed = seed;
-    h->m->rng_next = first_scene;
+    h->m->rng_next = first_scene;  // a draw-block index: scenes for dd_forward, first_scene * S for dd_forward_samples
   });
 }
 

@@ -509,9 +509,24 @@ __global__ __launch_bounds__(VU_NT, 1) void vproj_union_kernel(VprojArgs a) {
   }
   __syncthreads();
   // ---- the union of the rows' 3 x 3 neighbourhoods: bitmap over [key(first) - 65, key(last) + 65]
+  // (the tile's least and greatest key: the first and the last row while every count group has an image of its own;
+  // count groups that share an image (a.nimg < a.B: the samples of one scene) restart the pixel order within a tile.
+  // Every wave reduces the same 256 keys, so the result is workgroup-uniform without another barrier)
   const int nrow = min(VU_BM, total - m0);
-  const int kbase = g_key[0] - 65;
-  const int range = g_key[nrow - 1] + 66 - kbase;
+  int kmin = 0x7fffffff, kmax = -1;
+#pragma unroll
+  for (int j = 0; j < VU_BM / 64; ++j) {
+    const int k = g_key[lane + 64 * j];
+    kmax = max(kmax, k);
+    kmin = min(kmin, k >= 0 ? k : 0x7fffffff);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    kmin = min(kmin, __shfl_xor(kmin, o, 64));
+    kmax = max(kmax, __shfl_xor(kmax, o, 64));
+  }
+  const int kbase = kmin - 65;
+  const int range = kmax + 66 - kbase;
   if (range > VU_RBITS) {
     if (tid == 0 && sp == 0) a.fb[mt * 2 + nh] = 1u;  // the gathered kernel computes this tile
     return;
@@ -936,7 +951,10 @@ void launch_vproj(const VprojArgs& a, hipStream_t st) {
     throw std::runtime_error("vproj: operands must be 16-byte aligned");
   // buffer offsets are 32-bit byte offsets below 2^31: the map, the weight images and the union split's partials
   // (usplit slabs of B * cap rows)
-  if ((int64_t)a.B * kHW * kHW * kC * 4 >= (int64_t)kOOBv || (int64_t)kC * a.ldh * 2 >= (int64_t)kOOBv ||
+  // (the map holds nimg images; B counts the row groups, several of which may name one image)
+  const int nimg = a.nimg > 0 ? a.nimg : a.B;
+  if (nimg > a.B) throw std::runtime_error("vproj: more images than row groups");
+  if ((int64_t)nimg * kHW * kHW * kC * 4 >= (int64_t)kOOBv || (int64_t)kC * a.ldh * 2 >= (int64_t)kOOBv ||
       (a.union_stage && (int64_t)a.usplit * a.B * a.cap * kC * 4 >= (int64_t)kOOBv))
     throw std::runtime_error("vproj: operand extent >= 2 GiB");
   // two 128-channel halves per row tile: grid in groups of 8 tiles x 2 halves

@@ -181,7 +181,10 @@ class DiffusionDriveModel:
 
     def set_seed(self, seed: int, first_scene: int = 0):
         """Seed of the device noise draw (``noise="device"``); restarts its stream at global scene index
-        ``first_scene`` (dd_set_seed_at: a scene shard starting at that index draws the unsharded run's noise)."""
+        ``first_scene`` (dd_set_seed_at: a scene shard starting at that index draws the unsharded run's noise).
+        The position counts draw blocks of Q*P*2 normals: ``forward`` consumes one per scene, ``forward_samples``
+        ``num_samples`` per scene (sample s of scene b takes block position + b*num_samples + s), so a sharded
+        samples run passes ``first_scene * num_samples``."""
         if first_scene < 0:
             raise ValueError("first_scene must be >= 0")
         _lib.check(self.lib.dd_set_seed_at(self.handle, int(seed) & (2 ** 64 - 1), int(first_scene)), self.lib)
@@ -253,6 +256,88 @@ class DiffusionDriveModel:
         return res
 
     __call__ = forward
+
+    MAX_SAMPLES = _lib.MAX_SAMPLES
+
+    def forward_samples(self, features: Dict[str, torch.Tensor], num_samples: int, noise=None,
+                        steps: Optional[int] = None, heads: bool = False, modes: bool = False, best: bool = False,
+                        stream: Optional[torch.cuda.Stream] = None) -> Dict[str, torch.Tensor]:
+        """``num_samples`` trajectory draws per scene over ONE perception pass (dd_forward_samples): everything
+        before the trajectory head runs once for the B scenes, the head over the B * num_samples (scene, noise)
+        pairs. ``noise``: (B, S, Q, P, 2) start noises (sample s of scene b is ``forward``'s result for scene b with
+        ``noise[b, s]``), None (``torch.randn`` of that shape on the CPU, as ``forward`` draws its own) or
+        ``"device"`` (draw blocks of the ``set_seed`` stream). Returns ``trajectory`` (B, S, P, 3); ``modes`` adds
+        ``poses_reg`` (B, S, Q, P, 3) / ``poses_cls`` (B, S, Q); ``best`` adds ``best_trajectory`` (B, P, 3) and
+        ``best_index`` (B,) int32 = s * Q + q of the scene's candidate with the largest cls logit over all S * Q;
+        ``heads`` adds the per-scene BEV-semantic / agent outputs. Arguments are validated before any GPU work."""
+        cfg = self.config
+        Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
+        if isinstance(num_samples, bool) or not isinstance(num_samples, (int, np.integer)) or \
+                not 1 <= num_samples <= self.MAX_SAMPLES:
+            raise ValueError(f"num_samples must be an integer in 1..{self.MAX_SAMPLES}, got {num_samples!r}")
+        S = int(num_samples)
+        B = torch.as_tensor(features["status_feature"]).shape[0]
+        if isinstance(noise, str):
+            if noise != "device":
+                raise ValueError(f"noise must be a tensor, None or 'device', got {noise!r}")
+        elif noise is not None and tuple(torch.as_tensor(noise).shape) != (B, S, Q, P, 2):
+            raise ValueError(f"noise must be (B,{S},{Q},{P},2) with B = {B}, got {tuple(torch.as_tensor(noise).shape)}")
+        if noise is None:
+            noise = torch.randn((B, S, Q, P, 2))
+        dev = torch.device(f"cuda:{self.device}")
+        s = stream or torch.cuda.current_stream(dev)
+        with torch.cuda.stream(s):
+            return self._forward_samples_on(features, S, noise, steps, heads, modes, best, s)
+
+    def _forward_samples_on(self, features, S, noise, steps, heads, modes, best, s) -> Dict[str, torch.Tensor]:
+        cfg = self.config
+        cam = features["camera_feature"]
+        out_device = cam.device if isinstance(cam, torch.Tensor) else torch.device("cpu")
+        cam = self._dev(cam)
+        lid = self._dev(features["lidar_feature"])
+        st = self._dev(features["status_feature"])
+        B = st.shape[0]
+        Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
+        if tuple(cam.shape) != (B, 3, cfg.camera_height, cfg.camera_width):
+            raise ValueError(f"camera_feature must be (B,3,{cfg.camera_height},{cfg.camera_width}), got {tuple(cam.shape)}")
+        if tuple(lid.shape) != (B, cfg.lidar_in_channels, cfg.lidar_resolution_height, cfg.lidar_resolution_width):
+            raise ValueError(f"lidar_feature has shape {tuple(lid.shape)}")
+        if tuple(st.shape) != (B, 8):
+            raise ValueError(f"status_feature must be (B,8), got {tuple(st.shape)}")
+        nz = None if isinstance(noise, str) else self._dev(noise)
+        # as _forward_on: the caller may drop its tensors while stream s still reads them
+        for t in (cam, lid, st, nz):
+            if t is not None:
+                t.record_stream(s)
+        dev = cam.device
+        outs = _lib.DDSampleOutputs()
+        res = {"trajectory": torch.empty((B, S, P, 3), device=dev)}
+        outs.trajectory = res["trajectory"].data_ptr()
+        if modes:
+            res["poses_reg"] = torch.empty((B, S, Q, P, 3), device=dev)
+            res["poses_cls"] = torch.empty((B, S, Q), device=dev)
+            outs.poses_reg = res["poses_reg"].data_ptr()
+            outs.poses_cls = res["poses_cls"].data_ptr()
+        if best:
+            res["best_trajectory"] = torch.empty((B, P, 3), device=dev)
+            res["best_index"] = torch.empty((B,), device=dev, dtype=torch.int32)
+            outs.best_trajectory = res["best_trajectory"].data_ptr()
+            outs.best_index = res["best_index"].data_ptr()
+        if heads:
+            res["bev_semantic_map"] = torch.empty(
+                (B, 7, cfg.lidar_resolution_height // 2, cfg.lidar_resolution_width), device=dev)
+            res["agent_states"] = torch.empty((B, cfg.num_bounding_boxes, 5), device=dev)
+            res["agent_labels"] = torch.empty((B, cfg.num_bounding_boxes), device=dev)
+            outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
+            outs.agent_states = res["agent_states"].data_ptr()
+            outs.agent_labels = res["agent_labels"].data_ptr()
+        _lib.check(self.lib.dd_forward_samples(self.handle, cam.data_ptr(), lid.data_ptr(), st.data_ptr(),
+                                               nz.data_ptr() if nz is not None else None, B, S,
+                                               int(steps or cfg.denoise_steps), ctypes.byref(outs), s.cuda_stream),
+                   self.lib)
+        if out_device.type != "cuda":
+            res = {k: v.to(out_device) for k, v in res.items()}
+        return res
 
     def forward_train(self, features: Dict[str, torch.Tensor], targets: Optional[Dict[str, torch.Tensor]] = None,
                       timesteps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
@@ -514,6 +599,14 @@ class InFlightPlanner:
                              stream=self._current_stream())
 
     __call__ = forward
+
+    def forward_samples(self, features: Dict[str, torch.Tensor], num_samples: int, noise=None,
+                        steps: Optional[int] = None, heads: bool = False, modes: bool = False,
+                        best: bool = False) -> Dict[str, torch.Tensor]:
+        """``DiffusionDriveModel.forward_samples`` on the next lane."""
+        with self.next_lane() as m:
+            return m.forward_samples(features, num_samples, noise=noise, steps=steps, heads=heads, modes=modes,
+                                     best=best, stream=self._current_stream())
 
     def wait(self):
         """Make the current stream wait for every lane's queued work."""

@@ -13,6 +13,9 @@
  *                                                                  transfuser_model_v2.py:98-162,578-641
  *   dd_forward_ex  same, with the full output dict (bev_semantic_map, agent_states, agent_labels,
  *                  all-mode poses) of transfuser_model_v2.py:144-162,165-205
+ *   dd_forward_samples  S draws of the same forward's trajectory distribution per scene (S start noises through
+ *                  TrajectoryHead.forward_test, transfuser_model_v2.py:578-641) over ONE pass of everything before
+ *                  the head; the reference would run its whole forward once per draw
  *   dd_destroy  <- agent teardown (no reference counterpart; frees device memory)
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
@@ -67,6 +70,19 @@ typedef struct dd_outputs {
   float* agent_labels;     /* B x 30 */
 } dd_outputs;
 
+/* Outputs of dd_forward_samples (device pointers; NULL = not requested). */
+#define DD_MAX_SAMPLES 32   /* largest S of dd_forward_samples */
+typedef struct dd_sample_outputs {
+  float* trajectory;       /* B x S x P x 3: each sample's argmax mode (required) */
+  float* poses_reg;        /* B x S x Q x P x 3, last step / last layer */
+  float* poses_cls;        /* B x S x Q */
+  float* best_trajectory;  /* B x P x 3: the candidate with the largest cls logit over all S*Q of the scene */
+  int*   best_index;       /* B: s * Q + q of that candidate (first maximum on ties, as the per-sample argmax) */
+  float* bev_semantic_map; /* per scene, exactly as dd_outputs */
+  float* agent_states;
+  float* agent_labels;
+} dd_sample_outputs;
+
 /* Outputs of dd_forward_train (device pointers; NULL = not requested). */
 typedef struct dd_train_outputs {
   float* trajectory;       /* B x P x 3: the last layer's argmax mode (required) */
@@ -100,6 +116,24 @@ int dd_forward(dd_handle* h, const float* camera, const float* lidar, const floa
 int dd_forward_ex(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
                   int B, int steps, const dd_outputs* outs, void* stream);
 
+/* S trajectory samples per scene from one perception pass. The planner is a diffusion model: one start noise draws
+ * one trajectory from its output distribution, and everything before the trajectory head (trunks, GPT fusion, FPN,
+ * bev_proj, the tf decoder and its hoists, the optional heads: ~93 % of a forward) does not depend on the noise. This
+ * entry runs that part once for the B scenes and the head (TrajectoryHead.forward_test, transfuser_model_v2.py:578-641)
+ * over D = B * S decoder scenes, decoder scene d = b * S + s reading scene b's cross-BEV map, agent K / V and ego row.
+ * The reference has no counterpart: it would call V2TransfuserModel.forward S times (best-of-N under an external
+ * scorer, mode-diversity metrics, plan uncertainty). noise (B,S,Q,P,2): sample s of scene b is dd_forward's result for
+ * scene b with noise[b][s]. S in 1..DD_MAX_SAMPLES and at most the handle's chunk limit (128, $DDMI_MAX_CHUNK), else
+ * DD_ERR_INVALID before any device work; any B >= 1: scenes run in dd_forward's chunks (the backbone at the chunk's
+ * full batch) and the head in passes of at most chunk-limit decoder scenes. Every gemm mode, schedule and accepted
+ * num_modes; S = 1 is dd_forward_ex launch for launch. noise may be NULL: sample s of the call's scene b then takes
+ * draw block position + b * S + s of the handle's stream (a block = Q*P*2 normals; dd_forward consumes one block per
+ * scene, this call B * S), see dd_set_seed_at. best_trajectory / best_index: one more small launch picks each
+ * scene's best candidate over its S*Q (only when one of the two is requested). */
+int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, const float* status,
+                       const float* noise /* B x S x Q x P x 2, or NULL */, int B, int S, int steps,
+                       const dd_sample_outputs* outs, void* stream);
+
 /* The training-mode trajectory head over the eval-mode network, as a loss evaluator: replaces
  * V2TransfuserModel.forward(features, targets) with TrajectoryHead.forward_train (transfuser_model_v2.py:520-576) and
  * LossComputer (modules/multimodal_loss.py:119-168). forward_train's two random draws are inputs: timesteps (B
@@ -126,7 +160,10 @@ int dd_destroy(dd_handle* h);
  * seed 0. No reference counterpart (the reference draws on the CPU, transfuser_model_v2.py:593). */
 int dd_set_seed(dd_handle* h, unsigned long long seed);
 /* The same, with the stream positioned at global scene index first_scene: rank r of a scene-sharded job that
- * passes first_scene = r * (scenes per rank) draws exactly the noise of those scenes in an unsharded run. */
+ * passes first_scene = r * (scenes per rank) draws exactly the noise of those scenes in an unsharded run.
+ * first_scene is a DRAW-BLOCK index (a block = the Q*P*2 normals of one decoder scene): dd_forward consumes one
+ * block per scene, so for it blocks are scenes; dd_forward_samples consumes S per scene, so a sharded samples run
+ * passes first_scene * S. */
 int dd_set_seed_at(dd_handle* h, unsigned long long seed, unsigned long long first_scene);
 
 /* Last error message of the calling thread ("" if none). */
