@@ -113,10 +113,16 @@ __device__ inline void softmax_keys(mk_f16 st[NTL], int nkeys, float scale) {
 // o += V_h^T P^T (o: C layout, row = head dimension, column = query = lane % 32). The k16 step (t, s) takes
 // accumulator registers 8 s .. 8 s + 7 of tile t as the B fragment unchanged; the contraction order of its
 // 16 keys is the one the C layout implies - lane half hh, element e <-> key 32 t + 16 s + 4 hh + (e & 3) +
-// 8 (e >> 2) - and the A fragment (V^T) gathers the same keys: lane reads V[key][dim = lane % 32]
+// 8 (e >> 2) - and the A fragment (V^T) gathers the same keys: lane reads V[key][dim = lane % 32].
+// The probabilities are split as P * 2^12 (exact; <= 4096, far inside fp16) and the sum is scaled back: unscaled,
+// every P below 2^-3 has a subnormal lo part and every P below 2^-14 a subnormal hi part, an absolute 2^-25 per key
+// that meets V unscaled - one decoded query row in ~2000 came out 6e-5 .. 2.7e-4 off ("Uneven
+// channel scales"); scaled, the lo part is normal down to P = 2^-15 and the row error stays below 1.3e-5.
 template <int NTL, class VROW>
 __device__ inline void attn_pv_t(const mk_f16 st[NTL], mk_f16& o, VROW&& vrow, int nkeys) {
   const int lane = threadIdx.x & 63, li = lane & 31, hh = lane >> 5;
+  mk_f16 tacc;
+  zero_acc(tacc);
 #pragma unroll
   for (int t = 0; t < NTL; ++t)
 #pragma unroll
@@ -126,10 +132,12 @@ __device__ inline void attn_pv_t(const mk_f16 st[NTL], mk_f16& o, VROW&& vrow, i
       for (int e = 0; e < 8; ++e) {
         const int key = 32 * t + 16 * s + 4 * hh + (e & 3) + 8 * (e >> 2);
         a8[e] = key < nkeys ? vrow(key)[li] : 0.f;
-        b8[e] = st[t][8 * s + e];
+        b8[e] = st[t][8 * s + e] * 4096.f;
       }
-      mfma3(o, a8, b8);
+      mfma3(tacc, a8, b8);
     }
+#pragma unroll
+  for (int r = 0; r < 16; ++r) o[r] += tacc[r] * (1.f / 4096.f);
 }
 
 // the head's output O[query][h * 32 + dim] from o (C layout) into the split image dst; rows >= 31 zero
