@@ -53,6 +53,14 @@ class DDSampleOutputs(ctypes.Structure):
     ]
 
 
+class DDInputs(ctypes.Structure):
+    """dd_inputs: exactly one of camera_f32 / camera_u8 and one of lidar_f32 / lidar_u8 (include/ddmi.h)."""
+    _fields_ = [
+        ("camera_f32", c_void_p), ("camera_u8", c_void_p), ("lidar_f32", c_void_p), ("lidar_u8", c_void_p),
+        ("lidar_hist_max", ctypes.c_int), ("status", c_void_p), ("noise", c_void_p),
+    ]
+
+
 MAX_SAMPLES = 32  # DD_MAX_SAMPLES
 
 # name -> (restype, argtypes)
@@ -66,6 +74,12 @@ _SIGS = {
                                      ctypes.c_int, ctypes.POINTER(DDOutputs), c_void_p]),
     "dd_forward_samples": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDSampleOutputs), c_void_p]),
+    "dd_forward_in": (ctypes.c_int, [c_void_p, ctypes.POINTER(DDInputs), ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(DDOutputs), c_void_p]),
+    "dd_forward_samples_in": (ctypes.c_int, [c_void_p, ctypes.POINTER(DDInputs), ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_int, ctypes.POINTER(DDSampleOutputs), c_void_p]),
+    "dd_forward_train_in": (ctypes.c_int, [c_void_p, ctypes.POINTER(DDInputs), c_void_p, c_void_p, ctypes.c_int,
+                                           ctypes.c_float, ctypes.c_float, c_void_p, c_void_p]),
     "dd_destroy": (ctypes.c_int, [c_void_p]),
     "dd_last_error": (ctypes.c_char_p, []),
     "dd_set_profiling": (ctypes.c_int, [c_void_p, ctypes.c_int]),
@@ -102,6 +116,14 @@ _SIGS = {
     "dd_build_lidar": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_int,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_int, ctypes.c_longlong, c_void_p]),
+    "dd_build_camera_u8": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_int,
+                                          ctypes.c_int, c_void_p]),
+    "dd_build_lidar_u8": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, ctypes.c_int,
+                                         ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_float, ctypes.c_float,
+                                         ctypes.c_int, ctypes.c_longlong, c_void_p]),
+    "dd_op_stem_pool_u8": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, c_void_p,
+                                          c_void_p]),
     "dd_op_conv2d": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p]),

@@ -293,11 +293,16 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t st);
 // Fused stem conv 7x7/2 (Cin 4, Cout 64, f16x3) + bias + ReLU + maxpool 3x3/2 into pool_out (B,Hp,Wp,64)
 // (stem_pool.hip); false when `a` is not such a stem (then nothing is launched).
 // src (optional): the device word holding the address of the reference's NCHW input of src_c channels (read by the
-// kernel; the NHWC4 a.in is then unused).
+// kernel; the NHWC4 a.in is then unused). u8 = 0: that input is fp32; 1: the uint8 (B, H, W, 3) HWC image (src_c 3);
+// 2: the planar uint8 (B, src_c, H, W) tensor - byte k then stands for the fp32 value lut[k] (256 floats, device).
 bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st,
-                      const float* const* src = nullptr, int src_c = 0);
+                      const void* const* src = nullptr, int src_c = 0, int u8 = 0, const float* lut = nullptr);
 // Device-side input table: tab[0] = a, tab[1] = b (one thread; launched per forward outside the captured graph).
-void launch_set_ptrs(const float** tab, const float* a, const float* b, hipStream_t st);
+// The entries are untyped addresses: fp32 or uint8 features, as the stem form that reads them expects.
+void launch_set_ptrs(const void** tab, const void* a, const void* b, hipStream_t st);
+// The LiDAR byte table: lut[c] = (float)((double)min(c, hist_max) / (double)hist_max), c = 0..255 (the expression of
+// the feature builder's finalize pass, features.hip).
+void launch_lidar_lut(float* lut, int hist_max, hipStream_t st);
 // name of the kernel the last conv / GEMM dispatch on this thread went to ("conv_gemm", "conv_x3",
 // "conv_x5", "conv_x6"); the runtime's profiler attributes launch time per kernel with it
 const char* last_conv_kernel();
@@ -347,6 +352,10 @@ void launch_vproj(const VprojArgs& a, hipStream_t st);
 // Bandwidth / small kernels (elementwise.hip)
 // NCHW fp32 (B, C, H, W) -> NHWC padded to Cp channels (zero fill).
 void launch_nchw_to_nhwc(const float* in, float* out, int B, int C, int H, int W, int Cp, hipStream_t st);
+// uint8 features -> NHWC4 fp32 through a 256-entry fp32 table (byte k -> lut[k]; channels C..3 zero): hwc = 1 reads
+// the (B, H, W, C) HWC image (C = 3, the camera), hwc = 0 the planar (B, C, H, W) tensor (C = 1..4, the LiDAR counts).
+void launch_u8_to_nhwc4(const uint8_t* in, float* out, int B, int C, int H, int W, int hwc, const float* lut,
+                        hipStream_t st);
 // 3x3 / stride 2 / pad 1 max pool, NHWC contiguous.
 void launch_maxpool3x3s2(const float* in, float* out, int B, int H, int W, int C, int Ho, int Wo,
                          hipStream_t st);
@@ -407,6 +416,12 @@ void launch_camera_feature(const uint8_t* cams, int B, int H, int W, float* out,
 void launch_lidar_feature(const float* xyz, const int64_t* offs, int B, int C, float* out, int nb, float lo,
                           float hi, int ppm, float max_h, float split_h, int hist_max, int64_t max_points,
                           hipStream_t st);
+// The same features as bytes: the (B, oh, ow, 3) HWC resized image (s + 2) >> 2, and the planar (B, C, nb, nb)
+// clipped counts min(c, hist_max) (hist_max <= 255) - what the float forms divide by 255 / hist_max.
+void launch_camera_feature_u8(const uint8_t* cams, int B, int H, int W, uint8_t* out, int oh, int ow, hipStream_t st);
+void launch_lidar_feature_u8(const float* xyz, const int64_t* offs, int B, int C, uint8_t* out, int nb, float lo,
+                             float hi, int ppm, float max_h, float split_h, int hist_max, int64_t max_points,
+                             hipStream_t st);
 
 // ----------------------------------------------------------------------------------------
 // Decoder kernels (decoder.hip)

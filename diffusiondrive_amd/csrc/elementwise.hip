@@ -33,15 +33,68 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ in, float* __restr
   }
 }
 
-__global__ void set_ptrs_kernel(const float** tab, const float* a, const float* b) {
+__global__ void set_ptrs_kernel(const void** tab, const void* a, const void* b) {
   if (threadIdx.x == 0) {
     tab[0] = a;
     tab[1] = b;
   }
 }
 
-void launch_set_ptrs(const float** tab, const float* a, const float* b, hipStream_t st) {
+void launch_set_ptrs(const void** tab, const void* a, const void* b, hipStream_t st) {
   hipLaunchKernelGGL(set_ptrs_kernel, dim3(1), dim3(64), 0, st, tab, a, b);
+  DD_HIP_CHECK(hipGetLastError());
+}
+
+// ---------------------------------------------------------------- uint8 features
+// The LiDAR byte table (features.hip lidar_finalize_kernel's expression, one entry per byte value).
+__global__ void lidar_lut_kernel(float* __restrict__ lut, int hist_max) {
+  const int c = threadIdx.x;
+  const int cl = c > hist_max ? hist_max : c;
+  lut[c] = (float)((double)cl / (double)hist_max);
+}
+
+void launch_lidar_lut(float* lut, int hist_max, hipStream_t st) {
+  if (hist_max < 1 || hist_max > 255) throw std::invalid_argument("lidar table: hist_max must be in 1..255");
+  hipLaunchKernelGGL(lidar_lut_kernel, dim3(1), dim3(256), 0, st, lut, hist_max);
+  DD_HIP_CHECK(hipGetLastError());
+}
+
+// uint8 HWC (B, H, W, C) or planar (B, C, H, W) -> NHWC4 fp32 through the byte table (the routes that transpose:
+// the fp32 mode, DDMI_STEM_NCHW=0, four LiDAR channels). One thread per pixel, consecutive threads on consecutive
+// pixels: the byte loads of a wave fall in a few lines, the float4 stores are contiguous.
+template <int HWC>
+__global__ void u8_to_nhwc4_kernel(const uint8_t* __restrict__ in, float4* __restrict__ out, int64_t npix,
+                                   int64_t plane, int C, const float* __restrict__ lut) {
+  __shared__ float tab[256];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) tab[i] = lut[i];
+  __syncthreads();
+  for (int64_t p = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; p < npix; p += (int64_t)gridDim.x * blockDim.x) {
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (HWC) {
+      const uint8_t* s = in + p * C;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < C) v[c] = tab[s[c]];
+    } else {
+      const int64_t b = p / plane, hw = p - b * plane;
+      const uint8_t* s = in + b * C * plane + hw;
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (c < C) v[c] = tab[s[c * plane]];
+    }
+    out[p] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+void launch_u8_to_nhwc4(const uint8_t* in, float* out, int B, int C, int H, int W, int hwc, const float* lut,
+                        hipStream_t st) {
+  if (C < 1 || C > 4) throw std::runtime_error("u8_to_nhwc4: unsupported channel count");
+  const int64_t plane = (int64_t)H * W, n = (int64_t)B * plane;
+  float4* o = reinterpret_cast<float4*>(out);
+  if (hwc)
+    hipLaunchKernelGGL(u8_to_nhwc4_kernel<1>, dim3(grid_for(n)), dim3(256), 0, st, in, o, n, plane, C, lut);
+  else
+    hipLaunchKernelGGL(u8_to_nhwc4_kernel<0>, dim3(grid_for(n)), dim3(256), 0, st, in, o, n, plane, C, lut);
   DD_HIP_CHECK(hipGetLastError());
 }
 

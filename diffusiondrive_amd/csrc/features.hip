@@ -21,6 +21,8 @@
 
 namespace ddmi {
 
+// U8 = 1: the resized image itself, (B, oh, ow, 3) HWC bytes (s + 2) >> 2 (what ToTensor would divide by 255)
+template <int U8>
 __global__ void camera_feature_kernel(const uint8_t* __restrict__ cams, int H, int W, float* __restrict__ out,
                                       int oh, int ow, int f, int crop_top, int crop_side) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x;
@@ -47,10 +49,14 @@ __global__ void camera_feature_kernel(const uint8_t* __restrict__ cams, int H, i
   const uint8_t* r1 = r0 + (size_t)W * 3;
   const size_t plane = (size_t)oh * ow;
   float* o0 = out + (size_t)b * 3 * plane + (size_t)y * ow + x;
+  uint8_t* o8 = reinterpret_cast<uint8_t*>(out) + ((size_t)b * plane + (size_t)y * ow + x) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const int s = (int)r0[c] + (int)r0[3 + c] + (int)r1[c] + (int)r1[3 + c];
-    o0[c * plane] = (float)((s + 2) >> 2) / 255.0f;
+    if (U8)
+      o8[c] = (uint8_t)((s + 2) >> 2);
+    else
+      o0[c * plane] = (float)((s + 2) >> 2) / 255.0f;
   }
 }
 
@@ -62,15 +68,19 @@ __device__ inline int hist_bin(float v, double lo, double hi, double ppm, int nb
 }
 
 // xyz: per scene b, planar rows x[N_b], y[N_b], z[N_b] starting at 3 * offs[b] (NAVSIM lidar_pc[:3]).
+// U8 = 1 (hist_max = sat in 1..255): `counts` is the byte image itself, four pixels per word; a point raises its
+// pixel's byte by a compare-and-swap on the word unless the byte already holds sat, so the bytes end as
+// min(count, sat) with no carry into a neighbour and no finalize pass.
+template <int U8>
 __global__ void lidar_splat_kernel(const float* __restrict__ xyz, const int64_t* __restrict__ offs, int C,
                                    unsigned* __restrict__ counts, int nb, double lo, double hi, double ppm,
-                                   float max_h, float split_h) {
+                                   float max_h, float split_h, unsigned sat) {
   const int b = blockIdx.y;
   const int64_t p0 = offs[b], n = offs[b + 1] - p0;
   const float* px = xyz + 3 * p0;
   const float* py = px + n;
   const float* pz = py + n;
-  unsigned* cb = counts + (size_t)b * C * nb * nb;
+  unsigned* cb = counts + (U8 ? 0 : (size_t)b * C * nb * nb);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const float z = pz[i];
     if (!(z < max_h)) continue;  // transfuser_features.py:131 (NaN z dropped too)
@@ -85,7 +95,19 @@ __global__ void lidar_splat_kernel(const float* __restrict__ xyz, const int64_t*
     const int ix = hist_bin(px[i], lo, hi, ppm, nb);
     const int iy = hist_bin(py[i], lo, hi, ppm, nb);
     if (ix < 0 || iy < 0) continue;
-    atomicAdd(cb + ((size_t)ch * nb + ix) * nb + iy, 1u);
+    if (U8) {
+      const size_t pix = (((size_t)b * C + ch) * nb + ix) * nb + iy;
+      unsigned* w = cb + (pix >> 2);
+      const unsigned sh = 8u * (unsigned)(pix & 3);
+      unsigned old = *w;
+      while (((old >> sh) & 255u) < sat) {
+        const unsigned seen = atomicCAS(w, old, old + (1u << sh));
+        if (seen == old) break;
+        old = seen;
+      }
+    } else {
+      atomicAdd(cb + ((size_t)ch * nb + ix) * nb + iy, 1u);
+    }
   }
 }
 
@@ -97,7 +119,8 @@ __global__ void lidar_finalize_kernel(float* __restrict__ out, size_t n, int his
   out[i] = (float)((double)cl / (double)hist_max);
 }
 
-void launch_camera_feature(const uint8_t* cams, int B, int H, int W, float* out, int oh, int ow, hipStream_t st) {
+static void camera_feature(const uint8_t* cams, int B, int H, int W, void* out, int oh, int ow, bool u8,
+                           hipStream_t st) {
   constexpr int crop_top = 28, crop_side = 416;  // transfuser_features.py:68-70
   const int wl = W - 2 * crop_side;
   const int sw = 2 * wl + W, sh = H - 2 * crop_top;
@@ -109,8 +132,20 @@ void launch_camera_feature(const uint8_t* cams, int B, int H, int W, float* out,
                                 " image must down-scale to " + std::to_string(ow) + "x" + std::to_string(oh) +
                                 " by one even integer factor with camera seams on factor boundaries");
   dim3 grid((ow + 255) / 256, oh, B);
-  hipLaunchKernelGGL(camera_feature_kernel, grid, dim3(256), 0, st, cams, H, W, out, oh, ow, f, crop_top, crop_side);
+  float* o = static_cast<float*>(out);
+  if (u8)
+    hipLaunchKernelGGL(camera_feature_kernel<1>, grid, dim3(256), 0, st, cams, H, W, o, oh, ow, f, crop_top, crop_side);
+  else
+    hipLaunchKernelGGL(camera_feature_kernel<0>, grid, dim3(256), 0, st, cams, H, W, o, oh, ow, f, crop_top, crop_side);
   DD_HIP_CHECK(hipGetLastError());
+}
+
+void launch_camera_feature(const uint8_t* cams, int B, int H, int W, float* out, int oh, int ow, hipStream_t st) {
+  camera_feature(cams, B, H, W, out, oh, ow, false, st);
+}
+
+void launch_camera_feature_u8(const uint8_t* cams, int B, int H, int W, uint8_t* out, int oh, int ow, hipStream_t st) {
+  camera_feature(cams, B, H, W, out, oh, ow, true, st);
 }
 
 void launch_lidar_feature(const float* xyz, const int64_t* offs, int B, int C, float* out, int nb, float lo,
@@ -123,10 +158,29 @@ void launch_lidar_feature(const float* xyz, const int64_t* offs, int B, int C, f
   DD_HIP_CHECK(hipMemsetAsync(out, 0, n * sizeof(float), st));
   const int64_t per = max_points > 0 ? max_points : 1;
   const int bx = (int)std::min<int64_t>((per + 255) / 256, 1024);
-  hipLaunchKernelGGL(lidar_splat_kernel, dim3(bx, B), dim3(256), 0, st, xyz, offs, C,
-                     reinterpret_cast<unsigned*>(out), nb, (double)lo, (double)hi, (double)ppm, max_h, split_h);
+  hipLaunchKernelGGL(lidar_splat_kernel<0>, dim3(bx, B), dim3(256), 0, st, xyz, offs, C,
+                     reinterpret_cast<unsigned*>(out), nb, (double)lo, (double)hi, (double)ppm, max_h, split_h, 0u);
   DD_HIP_CHECK(hipGetLastError());
   hipLaunchKernelGGL(lidar_finalize_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out, n, hist_max);
+  DD_HIP_CHECK(hipGetLastError());
+}
+
+void launch_lidar_feature_u8(const float* xyz, const int64_t* offs, int B, int C, uint8_t* out, int nb, float lo,
+                             float hi, int ppm, float max_h, float split_h, int hist_max, int64_t max_points,
+                             hipStream_t st) {
+  if (B <= 0 || (C != 1 && C != 2) || nb <= 0 || hist_max <= 0 || hist_max > 255)
+    throw std::invalid_argument("lidar feature (uint8): bad arguments (hist_max must be in 1..255)");
+  if ((int64_t)((hi - lo) * ppm) != nb) throw std::invalid_argument("lidar feature: (hi - lo) * ppm != resolution");
+  const size_t n = (size_t)B * C * nb * nb;
+  // the splat updates whole words of the byte image
+  if ((n & 3) || (reinterpret_cast<uintptr_t>(out) & 3))
+    throw std::invalid_argument("lidar feature (uint8): the output must be 4-byte aligned and a multiple of 4 bytes");
+  DD_HIP_CHECK(hipMemsetAsync(out, 0, n, st));
+  const int64_t per = max_points > 0 ? max_points : 1;
+  const int bx = (int)std::min<int64_t>((per + 255) / 256, 1024);
+  hipLaunchKernelGGL(lidar_splat_kernel<1>, dim3(bx, B), dim3(256), 0, st, xyz, offs, C,
+                     reinterpret_cast<unsigned*>(out), nb, (double)lo, (double)hi, (double)ppm, max_h, split_h,
+                     (unsigned)hist_max);
   DD_HIP_CHECK(hipGetLastError());
 }
 

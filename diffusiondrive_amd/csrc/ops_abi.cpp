@@ -189,8 +189,19 @@ int dd_op_conv2d_x3(const float* in, int B, int H, int W, int Cin, const float* 
   });
 }
 
-static int dd_op_stem_pool_impl(const float* in, int src_c, int B, int H, int W, const float* wgt, const float* bias,
-                                float* out, int prec, unsigned* flags, void* stream);
+// u8: 0 = in is fp32, 1 = uint8 HWC, 2 = uint8 planar (lut: the bytes' 256 fp32 values)
+static int dd_op_stem_pool_impl(const void* in, int src_c, int B, int H, int W, const float* wgt, const float* bias,
+                                float* out, int prec, unsigned* flags, void* stream, int u8 = 0,
+                                const float* lut = nullptr);
+
+int dd_op_stem_pool_u8(const uint8_t* in, int layout, int B, int C, int H, int W, const float* lut, const float* wgt,
+                       const float* bias, float* out, int prec, unsigned* flags, void* stream) {
+  if (!in || !lut || (layout != 0 && layout != 1) || C < 1 || C > 3 || (layout == 0 && C != 3))
+    return op_guard([&] {
+      throw std::invalid_argument("stem_pool_u8: layout 0 (HWC, C = 3) or 1 (planar, C = 1..3), in and lut non-null");
+    });
+  return dd_op_stem_pool_impl(in, C, B, H, W, wgt, bias, out, prec, flags, stream, layout == 0 ? 1 : 2, lut);
+}
 
 int dd_op_stem_pool_x3(const float* in, int B, int H, int W, const float* wgt, const float* bias, float* out,
                        unsigned* flags, void* stream) {
@@ -208,8 +219,8 @@ int dd_op_stem_pool(const float* in, int B, int H, int W, const float* wgt, cons
   return dd_op_stem_pool_impl(in, 0, B, H, W, wgt, bias, out, prec, flags, stream);
 }
 
-static int dd_op_stem_pool_impl(const float* in, int src_c, int B, int H, int W, const float* wgt, const float* bias,
-                                float* out, int prec, unsigned* flags, void* stream) {
+static int dd_op_stem_pool_impl(const void* in, int src_c, int B, int H, int W, const float* wgt, const float* bias,
+                                float* out, int prec, unsigned* flags, void* stream, int u8, const float* lut) {
   return op_guard([&] {
     if (prec != 0 && prec != 1) throw std::invalid_argument("stem_pool: prec must be 0 (f16x3) or 1 (bf16)");
     const int Cin = 4, Cout = 64, K = 7 * 7 * Cin;
@@ -220,7 +231,7 @@ static int dd_op_stem_pool_impl(const float* in, int src_c, int B, int H, int W,
     const SplitW x = prep_split(ar, hw.data(), Cout, K);
     ar.upload();
     ConvArgs a;
-    a.in = in;
+    a.in = u8 ? nullptr : static_cast<const float*>(in);
     a.in_sw = Cin;
     a.in_sh = (int64_t)W * Cin;
     a.in_sn = (int64_t)H * W * Cin;
@@ -246,14 +257,14 @@ static int dd_op_stem_pool_impl(const float* in, int src_c, int B, int H, int W,
     a.flags = flags;
     const int hp = (a.Ho + 2 - 3) / 2 + 1, wp = (a.Wo + 2 - 3) / 2 + 1;
     // NCHW input of src_c channels: the kernel reads its address from a device word
-    const float** word = nullptr;
+    const void** word = nullptr;
     if (src_c) {
-      DD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&word), sizeof(const float*)));
-      DD_HIP_CHECK(hipMemcpy(word, &in, sizeof(const float*), hipMemcpyHostToDevice));
+      DD_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&word), sizeof(const void*)));
+      DD_HIP_CHECK(hipMemcpy(word, &in, sizeof(const void*), hipMemcpyHostToDevice));
     }
     bool ok = false;
     try {
-      ok = launch_stem_pool(a, out, hp, wp, S(stream), src_c ? word : nullptr, src_c);
+      ok = launch_stem_pool(a, out, hp, wp, S(stream), src_c ? word : nullptr, src_c, u8, lut);
       DD_HIP_CHECK(hipStreamSynchronize(S(stream)));  // the split images die with `ar`
     } catch (...) {
       if (word) (void)hipFree(word);
@@ -279,6 +290,24 @@ int dd_build_lidar(const float* xyz, const int64_t* offsets, int B, int channels
     if (!offsets || !out || (!xyz && max_points > 0)) throw std::invalid_argument("null pointer");
     launch_lidar_feature(xyz, offsets, B, channels, out, resolution, range_lo, range_hi, pixels_per_meter,
                          max_height, split_height, hist_max, max_points, S(stream));
+  });
+}
+
+int dd_build_camera_u8(const uint8_t* cams, int B, int src_h, int src_w, uint8_t* out, int out_h, int out_w,
+                       void* stream) {
+  return op_guard([&] {
+    if (!cams || !out) throw std::invalid_argument("null pointer");
+    launch_camera_feature_u8(cams, B, src_h, src_w, out, out_h, out_w, S(stream));
+  });
+}
+
+int dd_build_lidar_u8(const float* xyz, const int64_t* offsets, int B, int channels, uint8_t* out, int resolution,
+                      float range_lo, float range_hi, int pixels_per_meter, float max_height, float split_height,
+                      int hist_max, long long max_points, void* stream) {
+  return op_guard([&] {
+    if (!offsets || !out || (!xyz && max_points > 0)) throw std::invalid_argument("null pointer");
+    launch_lidar_feature_u8(xyz, offsets, B, channels, out, resolution, range_lo, range_hi, pixels_per_meter,
+                            max_height, split_height, hist_max, max_points, S(stream));
   });
 }
 

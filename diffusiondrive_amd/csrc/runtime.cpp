@@ -206,7 +206,22 @@ class Model {
   int vproj_umax = 1 << 30;  // DDMI_VPROJ_UMAX (tests): tiles with a larger union take the gathered fallback
   int vproj_usplit_env = 0;  // DDMI_VPROJ_USPLIT (1, 2, 4, 8): the union form's K split, else chosen from B
   bool stem_nchw = true;             // see use_nchw_stem
-  const float** in_tab = nullptr;    // device input table: [0] camera, [1] LiDAR of the current forward
+  const void** in_tab = nullptr;     // device input table: [0] camera, [1] LiDAR of the current forward (untyped
+                                     // addresses: fp32 or uint8 features, see InKinds)
+  // uint8 features (dd_forward_in and its siblings): the element type of the current call's camera / LiDAR input,
+  // set for the duration of one call. A uint8 camera is the (B, cam_h, cam_w, 3) HWC image, byte k = k / 255; a
+  // uint8 LiDAR the planar (B, C, lidar_h, lidar_w) clipped counts, byte c = min(c, hist_max) / hist_max. The stems
+  // (or the transposing passes) widen the bytes through the two 256-entry fp32 tables of in_lut: [0, 256) the
+  // camera's, written once at create; [256, 512) the LiDAR's, rewritten on the stream ahead of the forward when
+  // hist_max changes (lut_hist_max = the value it holds).
+  struct InKinds {
+    bool cam_u8 = false, lid_u8 = false;
+    int hist_max = 0;
+  } kinds;
+  float* in_lut = nullptr;
+  int lut_hist_max = 0;
+  size_t cam_esz() const { return kinds.cam_u8 ? 1 : sizeof(float); }
+  size_t lid_esz() const { return kinds.lid_u8 ? 1 : sizeof(float); }
   const char* force_class = nullptr;  // profiling class of the next launch (else the chosen kernel)
   // bev_proj (DDMI_BEVPROJ): 2 "fused" = one bevproj.hip pass (f16x3 / bf16 modes; fp32 mode uses 1),
   // 1 "lowres" = keyval half at 8 x 8, upsample, K = 64 GEMM, LayerNorm; 0 "concat" = concat at 64 x 64
@@ -337,6 +352,14 @@ class Model {
     DD_HIP_CHECK(hipMalloc(&in_tab, 4 * sizeof(float*)));
     // zeroed on the handle's own stream and waited for: ordered before any forward, on whichever stream it runs
     DD_HIP_CHECK(hipMemsetAsync(in_tab, 0, 4 * sizeof(float*), st_own));
+    {
+      // the camera byte table: float(k) / 255.0f, correctly rounded (torch's uint8 -> .float().div(255), and what the
+      // feature builder's camera kernel writes); the LiDAR half is filled before the first uint8 LiDAR forward
+      float lut[512] = {};
+      for (int k = 0; k < 256; ++k) lut[k] = (float)k / 255.0f;
+      DD_HIP_CHECK(hipMalloc(&in_lut, sizeof(lut)));
+      DD_HIP_CHECK(hipMemcpy(in_lut, lut, sizeof(lut), hipMemcpyHostToDevice));
+    }
     if (const char* e = getenv("DDMI_BEVPROJ")) {
       if (!strcmp(e, "fused")) bevproj_mode = 2;
       else if (!strcmp(e, "lowres")) bevproj_mode = 1;
@@ -408,6 +431,7 @@ class Model {
     if (st_side) release_stream(device, st_side);
     if (num_flags) (void)hipFree(num_flags);
     if (in_tab) (void)hipFree(in_tab);
+    if (in_lut) (void)hipFree(in_lut);
     if (tf_mk_layers) (void)hipFree(tf_mk_layers);
     if (ac_dev) (void)hipFree(ac_dev);
     if (train_part) (void)hipFree(train_part);
@@ -1222,17 +1246,24 @@ class Model {
   // otherwise the conv into `stem` and the pool from it
   // in_idx / in_c: with the NCHW stem (use_nchw_stem) the kernel reads the caller's NCHW input of in_c channels
   // through the device input table entry in_idx instead of the NHWC4 copy (which is then never made)
+  // in_u8: that input is uint8 (1 = HWC image, 2 = planar), widened in the kernel's patch load through lut
   void stem_and_pool(const Conv& c, const float* in4, int N, int H, int Wd, float* stem, float* pool, int hp, int wp,
-                     int in_idx, int in_c) {
+                     int in_idx, int in_c, int in_u8 = 0, const float* lut = nullptr) {
     const int hs = (H + 2 * c.pad - c.k) / c.stride + 1, ws = (Wd + 2 * c.pad - c.k) / c.stride + 1;
     ConvArgs a = conv_args(c, in4, (int64_t)H * Wd * c.cin, (int64_t)Wd * c.cin, c.cin, N, H, Wd, stem,
                            (int64_t)hs * ws * c.cout, (int64_t)ws * c.cout, c.cout, true, nullptr, 0, 0, 0);
     bool done = false;
     const double fl = 2.0 * N * hs * ws * (double)c.cout * c.k * c.k * c.cin_real;
     const bool nchw = use_nchw_stem();
+    // byte model: the input once at its element size (the NHWC4 copy has 4 floats per pixel, the NCHW tensor in_c;
+    // a uint8 input 1 B per element), the pooled map, the weight image
+    const double in_bytes = nchw ? (double)N * H * Wd * in_c * (in_u8 ? 1.0 : 4.0) : (double)N * H * Wd * c.cin * 4.0;
+    const double wb = (a.wh && a.prec == 1) ? 2.0 : 4.0;
+    const double bytes = in_bytes + 4.0 * N * hp * wp * c.cout + wb * (double)c.cout * c.k * c.k * c.cin;
     launch("stem_pool", fl, [&] {
-      done = launch_stem_pool(a, pool, hp, wp, st, nchw ? in_tab + in_idx : nullptr, nchw ? in_c : 0);
-    });
+      done = launch_stem_pool(a, pool, hp, wp, st, nchw ? in_tab + in_idx : nullptr, nchw ? in_c : 0,
+                              nchw ? in_u8 : 0, lut);
+    }, nullptr, bytes);
     if (done) return;
     if (nchw) throw std::runtime_error("stem: the NCHW-input fused stem refused this shape (DDMI_STEM_NCHW=0 avoids it)");
     conv_c(c, in4, N, H, Wd, stem, true);
@@ -1679,8 +1710,11 @@ class Model {
     const int hl2 = (hl + 2 - 3) / 2 + 1, wl2 = (wl + 2 - 3) / 2 + 1;
     float* pool_l = buf("lid_pool", (size_t)B * hl2 * wl2 * 64);
     fork();
-    side([&] { stem_and_pool(lid.stem, lid4, B, HL, WL, stem_l, pool_l, hl2, wl2, 1, cfg.lidar_channels); });
-    stem_and_pool(img.stem, cam4, B, HC, WC, stem_i, pool_i, hi2, wi2, 0, 3);
+    side([&] {
+      stem_and_pool(lid.stem, lid4, B, HL, WL, stem_l, pool_l, hl2, wl2, 1, cfg.lidar_channels, kinds.lid_u8 ? 2 : 0,
+                    in_lut + 256);
+    });
+    stem_and_pool(img.stem, cam4, B, HC, WC, stem_i, pool_i, hi2, wi2, 0, 3, kinds.cam_u8 ? 1 : 0, in_lut);
 
     // ---- 4 scales: trunk stages (image on the main stream, LiDAR beside it) + GPT fusion
     float* xi = pool_i;
@@ -2158,12 +2192,19 @@ class Model {
 
   // noise == NULL: draw it on the device, draw blocks [block0, block0 + B * samples) of the handle's stream (a
   // block = the Q * P * 2 normals of one decoder scene; sample s of the chunk's scene b takes block0 + b * samples + s)
-  void stage_inputs(const float* camera, const float* lidar, const float* status, const float* noise, int B,
+  // camera / lidar: fp32 NCHW or uint8 (kinds)
+  void stage_inputs(const void* camera, const void* lidar, const float* status, const float* noise, int B,
                     uint64_t block0) {
     float* st_in = buf("in_status", (size_t)B * 8);
     const size_t blk = (size_t)cfg.num_modes * cfg.num_poses * 2;
     const size_t per = blk * (size_t)samples;  // noise floats per scene
     float* nz = buf("in_noise", (size_t)B * per);
+    if (kinds.lid_u8 && lut_hist_max != kinds.hist_max) {
+      // a small launch on the stream ahead of the forward (never a node of a captured graph): the handle's earlier
+      // forwards, which read the table, are ordered before this one (OnStream)
+      launch("misc", 0, [&] { launch_lidar_lut(in_lut + 256, kinds.hist_max, st); });
+      lut_hist_max = kinds.hist_max;
+    }
     if (use_nchw_stem()) {
       // the stems read the caller's NCHW tensors in place: only their addresses go to the device table (the
       // captured graph reads them from there); the caller's buffers outlive the forward (stream order)
@@ -2171,8 +2212,20 @@ class Model {
     } else {
       float* cam4 = buf("in_cam4", (size_t)B * cfg.cam_h * cfg.cam_w * 4);
       float* lid4 = buf("in_lid4", (size_t)B * cfg.lidar_h * cfg.lidar_w * 4);
-      launch("misc", 0, [&] { launch_nchw_to_nhwc(camera, cam4, B, 3, cfg.cam_h, cfg.cam_w, 4, st); });
-      launch("misc", 0, [&] { launch_nchw_to_nhwc(lidar, lid4, B, cfg.lidar_channels, cfg.lidar_h, cfg.lidar_w, 4, st); });
+      launch("misc", 0, [&] {
+        if (kinds.cam_u8)
+          launch_u8_to_nhwc4(static_cast<const uint8_t*>(camera), cam4, B, 3, cfg.cam_h, cfg.cam_w, 1, in_lut, st);
+        else
+          launch_nchw_to_nhwc(static_cast<const float*>(camera), cam4, B, 3, cfg.cam_h, cfg.cam_w, 4, st);
+      });
+      launch("misc", 0, [&] {
+        if (kinds.lid_u8)
+          launch_u8_to_nhwc4(static_cast<const uint8_t*>(lidar), lid4, B, cfg.lidar_channels, cfg.lidar_h, cfg.lidar_w, 0,
+                             in_lut + 256, st);
+        else
+          launch_nchw_to_nhwc(static_cast<const float*>(lidar), lid4, B, cfg.lidar_channels, cfg.lidar_h, cfg.lidar_w, 4,
+                              st);
+      });
     }
     DD_HIP_CHECK(hipMemcpyAsync(st_in, status, sizeof(float) * B * 8, hipMemcpyDeviceToDevice, st));
     if (train) {
@@ -2203,7 +2256,8 @@ class Model {
   // The forward of B scenes. More than max_chunk scenes run as ceil(B / max_chunk) equal chunks (the last one
   // may be shorter) through the same per-chunk path, in order on the handle's stream; every kernel of the path
   // is per scene, so a chunked forward equals the forward of its chunks scene for scene.
-  void forward(const float* camera, const float* lidar, const float* status, const float* noise, int B, int steps,
+  // camera / lidar: fp32 or uint8 as `kinds` says (chunk offsets are in bytes of the input's element type)
+  void forward(const void* camera, const void* lidar, const float* status, const float* noise, int B, int steps,
                const Outs& o, hipStream_t caller) {
     if (B <= 0) throw std::invalid_argument("batch must be positive");
     if (steps <= 0 || steps > (schedule == DD_SCHED_VANILLA ? 1000 : cfg.step_span))
@@ -2216,6 +2270,9 @@ class Model {
     for (int b0 = 0; b0 < B; b0 += chunk) {
       const int n = std::min(chunk, B - b0);
       auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+      auto offb = [&](const void* p, size_t per, size_t esz) {
+        return static_cast<const void*>(static_cast<const char*>(p) + (size_t)b0 * per * esz);
+      };
       auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
       Outs oc;
       oc.traj = offw(o.traj, (size_t)P * 3);
@@ -2224,8 +2281,8 @@ class Model {
       oc.sem = offw(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
       oc.ag_states = offw(o.ag_states, (size_t)30 * 5);
       oc.ag_labels = offw(o.ag_labels, (size_t)30);
-      forward_chunk(off(camera, (size_t)3 * cfg.cam_h * cfg.cam_w),
-                    off(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w), off(status, 8),
+      forward_chunk(offb(camera, (size_t)3 * cfg.cam_h * cfg.cam_w, cam_esz()),
+                    offb(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w, lid_esz()), off(status, 8),
                     off(noise, (size_t)Q * P * 2), n, steps, oc, caller, rng_next + (uint64_t)b0);
     }
     if (!noise) rng_next += (uint64_t)B;
@@ -2234,7 +2291,7 @@ class Model {
   // S trajectory samples per scene over one perception pass (dd_forward_samples): the scene chunks of forward(), the
   // backbone at the chunk's full batch, the trajectory head over decoder scenes d = b * S + s in passes of at most
   // max_chunk of them (forward_body). noise (B,S,Q,P,2) or nullptr: draw blocks [rng_next, rng_next + B * S).
-  void forward_samples(const float* camera, const float* lidar, const float* status, const float* noise, int B, int S,
+  void forward_samples(const void* camera, const void* lidar, const float* status, const float* noise, int B, int S,
                        int steps, const Outs& o, hipStream_t caller) {
     if (S < 1 || S > DD_MAX_SAMPLES)
       throw std::invalid_argument("dd_forward_samples: S must be in [1, " + std::to_string(DD_MAX_SAMPLES) + "], got " +
@@ -2262,6 +2319,9 @@ class Model {
     for (int b0 = 0; b0 < B; b0 += chunk) {
       const int n = std::min(chunk, B - b0);
       auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+      auto offb = [&](const void* p, size_t per, size_t esz) {
+        return static_cast<const void*>(static_cast<const char*>(p) + (size_t)b0 * per * esz);
+      };
       auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
       Outs oc;
       oc.traj = offw(o.traj, (size_t)S * P * 3);
@@ -2272,8 +2332,8 @@ class Model {
       oc.sem = offw(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
       oc.ag_states = offw(o.ag_states, (size_t)30 * 5);
       oc.ag_labels = offw(o.ag_labels, (size_t)30);
-      forward_chunk(off(camera, (size_t)3 * cfg.cam_h * cfg.cam_w),
-                    off(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w), off(status, 8),
+      forward_chunk(offb(camera, (size_t)3 * cfg.cam_h * cfg.cam_w, cam_esz()),
+                    offb(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w, lid_esz()), off(status, 8),
                     off(noise, (size_t)S * Q * P * 2), n, steps, oc, caller, rng_next + (uint64_t)b0 * S);
     }
     if (!noise) rng_next += (uint64_t)B * S;
@@ -2282,7 +2342,7 @@ class Model {
   // The training-mode trajectory head (forward_train, transfuser_model_v2.py:520-576) over the eval-mode network, as
   // a loss evaluator: per-scene timesteps / noise in, every layer's poses out, and with targets the LossComputer losses
   // (multimodal_loss.py:119-168) of both layers and their sum (loss[3]), reduced over the whole batch after its chunks.
-  void forward_train(const float* camera, const float* lidar, const float* status, const float* noise,
+  void forward_train(const void* camera, const void* lidar, const float* status, const float* noise,
                      const int* timesteps, const float* target, int B, const Outs& o, float* loss, float cls_w,
                      float reg_w, hipStream_t caller) {
     if (B <= 0) throw std::invalid_argument("batch must be positive");
@@ -2310,6 +2370,9 @@ class Model {
     for (int b0 = 0; b0 < B; b0 += chunk) {
       const int n = std::min(chunk, B - b0);
       auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+      auto offb = [&](const void* p, size_t per, size_t esz) {
+        return static_cast<const void*>(static_cast<const char*>(p) + (size_t)b0 * per * esz);
+      };
       auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
       Outs oc;
       oc.traj = offw(o.traj, (size_t)P * 3);
@@ -2323,8 +2386,8 @@ class Model {
       }
       train_t = timesteps + b0;
       train_target = target ? target + (size_t)b0 * P * 3 : nullptr;
-      forward_chunk(off(camera, (size_t)3 * cfg.cam_h * cfg.cam_w),
-                    off(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w), off(status, 8),
+      forward_chunk(offb(camera, (size_t)3 * cfg.cam_h * cfg.cam_w, cam_esz()),
+                    offb(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w, lid_esz()), off(status, 8),
                     off(noise, (size_t)Q * P * 2), n, 1, oc, caller, 0);
     }
     if (target) {
@@ -2364,7 +2427,7 @@ class Model {
     }
   };
 
-  void forward_chunk(const float* camera, const float* lidar, const float* status, const float* noise, int B,
+  void forward_chunk(const void* camera, const void* lidar, const float* status, const float* noise, int B,
                      int steps, const Outs& o, hipStream_t caller, uint64_t scene0) {
     DD_HIP_CHECK(hipSetDevice(device));
     DD_TRACE("forward_chunk B=%d steps=%d caller=%p use_side=%d", B, steps, (void*)caller, (int)use_side);
@@ -2379,7 +2442,7 @@ class Model {
     const std::string key = std::to_string(B) + "/" + std::to_string(steps) + "/" + std::to_string(heads) + "/g" +
                             std::to_string(gemm_mode) + "/s" + std::to_string(schedule) +
                             (train ? (train_target ? "/train1" : "/train0") : "") + "/x" + std::to_string(samples) +
-                            (want_best ? "/best" : "");
+                            (want_best ? "/best" : "") + "/i" + (kinds.cam_u8 ? "b" : "f") + (kinds.lid_u8 ? "b" : "f");
     if (use_graph && !profiling && known_shapes.count(key)) {
       if (graph_gen != generation || programs.size() > 8) {
         // an earlier replay may still run (on the caller's stream in direct mode): ev_out marks the last forward
@@ -2495,6 +2558,54 @@ static int guarded(F&& f) {
   }
 }
 
+// ---- inputs: every forward entry point goes through a dd_inputs descriptor (the float-pointer entries fill one)
+namespace {
+struct InDesc {
+  const void* cam = nullptr;
+  const void* lid = nullptr;
+  ddmi::Model::InKinds kinds;
+};
+// Exactly one pointer per sensor, hist_max in 1..255 with a uint8 LiDAR: checked before any device work, the
+// offending field named.
+InDesc check_inputs(const char* who, const dd_inputs* in) {
+  if (!in) throw std::invalid_argument(std::string(who) + ": null inputs descriptor");
+  auto one = [&](const void* f, const void* u, const char* nf, const char* nu) {
+    if ((f != nullptr) == (u != nullptr))
+      throw std::invalid_argument(std::string(who) + ": dd_inputs." + nf + " / " + nu + ": exactly one must be set, " +
+                                  (f ? "both are" : "neither is (null input pointer)"));
+  };
+  one(in->camera_f32, in->camera_u8, "camera_f32", "camera_u8");
+  one(in->lidar_f32, in->lidar_u8, "lidar_f32", "lidar_u8");
+  InDesc d;
+  d.kinds.cam_u8 = in->camera_u8 != nullptr;
+  d.kinds.lid_u8 = in->lidar_u8 != nullptr;
+  d.cam = d.kinds.cam_u8 ? static_cast<const void*>(in->camera_u8) : in->camera_f32;
+  d.lid = d.kinds.lid_u8 ? static_cast<const void*>(in->lidar_u8) : in->lidar_f32;
+  if (d.kinds.lid_u8) {
+    if (in->lidar_hist_max < 1 || in->lidar_hist_max > 255)
+      throw std::invalid_argument(std::string(who) + ": dd_inputs.lidar_hist_max = " +
+                                  std::to_string(in->lidar_hist_max) + " is not in 1..255");
+    d.kinds.hist_max = in->lidar_hist_max;
+  }
+  return d;
+}
+// the call's input kinds on the handle for the duration of the call
+struct KindScope {
+  Model& m;
+  KindScope(Model& mm, const ddmi::Model::InKinds& k) : m(mm) { m.kinds = k; }
+  ~KindScope() { m.kinds = ddmi::Model::InKinds(); }
+};
+dd_inputs float_inputs(const float* camera, const float* lidar, const float* status, const float* noise) {
+  dd_inputs in;
+  std::memset(&in, 0, sizeof(in));
+  in.camera_f32 = camera;
+  in.lidar_f32 = lidar;
+  in.status = status;
+  in.noise = noise;
+  return in;
+}
+}  // namespace
+
 extern "C" {
 
 void dd_default_config(dd_config* c) {
@@ -2549,10 +2660,10 @@ int dd_create(const dd_config* cfg, const void* blob, size_t bytes, int device, 
   });
 }
 
-int dd_forward_ex(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
-                  int B, int steps, const dd_outputs* outs, void* stream) {
+int dd_forward_in(dd_handle* h, const dd_inputs* in, int B, int steps, const dd_outputs* outs, void* stream) {
   return guarded([&] {
     if (!h || !outs) throw std::invalid_argument("dd_forward_ex: null handle/outputs");
+    const InDesc d = check_inputs("dd_forward_in", in);
     std::lock_guard<std::mutex> lk(h->mu);
 #ifdef DDMI_SEGV_TRACE
     signal(SIGSEGV, ddmi_segv);  // the HSA runtime may have replaced it since the library loaded
@@ -2564,14 +2675,22 @@ int dd_forward_ex(dd_handle* h, const float* camera, const float* lidar, const f
     o.sem = outs->bev_semantic_map;
     o.ag_states = outs->agent_states;
     o.ag_labels = outs->agent_labels;
-    h->m->forward(camera, lidar, status, noise, B, steps, o, static_cast<hipStream_t>(stream));
+    KindScope ks(*h->m, d.kinds);
+    h->m->forward(d.cam, d.lid, in->status, in->noise, B, steps, o, static_cast<hipStream_t>(stream));
   });
 }
 
-int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
-                       int B, int S, int steps, const dd_sample_outputs* outs, void* stream) {
+int dd_forward_ex(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
+                  int B, int steps, const dd_outputs* outs, void* stream) {
+  const dd_inputs in = float_inputs(camera, lidar, status, noise);
+  return dd_forward_in(h, &in, B, steps, outs, stream);
+}
+
+int dd_forward_samples_in(dd_handle* h, const dd_inputs* in, int B, int S, int steps, const dd_sample_outputs* outs,
+                          void* stream) {
   return guarded([&] {
     if (!h || !outs) throw std::invalid_argument("dd_forward_samples: null handle/outputs");
+    const InDesc d = check_inputs("dd_forward_samples_in", in);
     std::lock_guard<std::mutex> lk(h->mu);
     Model::Outs o;
     o.traj = outs->trajectory;
@@ -2582,15 +2701,22 @@ int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, co
     o.sem = outs->bev_semantic_map;
     o.ag_states = outs->agent_states;
     o.ag_labels = outs->agent_labels;
-    h->m->forward_samples(camera, lidar, status, noise, B, S, steps, o, static_cast<hipStream_t>(stream));
+    KindScope ks(*h->m, d.kinds);
+    h->m->forward_samples(d.cam, d.lid, in->status, in->noise, B, S, steps, o, static_cast<hipStream_t>(stream));
   });
 }
 
-int dd_forward_train(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
-                     const int* timesteps, const float* target_traj, int B, float cls_weight, float reg_weight,
-                     const dd_train_outputs* outs, void* stream) {
+int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
+                       int B, int S, int steps, const dd_sample_outputs* outs, void* stream) {
+  const dd_inputs in = float_inputs(camera, lidar, status, noise);
+  return dd_forward_samples_in(h, &in, B, S, steps, outs, stream);
+}
+
+int dd_forward_train_in(dd_handle* h, const dd_inputs* in, const int* timesteps, const float* target_traj, int B,
+                        float cls_weight, float reg_weight, const dd_train_outputs* outs, void* stream) {
   return guarded([&] {
     if (!h || !outs) throw std::invalid_argument("dd_forward_train: null handle/outputs");
+    const InDesc d = check_inputs("dd_forward_train_in", in);
     std::lock_guard<std::mutex> lk(h->mu);
     Model::Outs o;
     o.traj = outs->trajectory;
@@ -2601,9 +2727,17 @@ int dd_forward_train(dd_handle* h, const float* camera, const float* lidar, cons
       o.reg_l[l] = outs->poses_reg[l];
       o.cls_l[l] = outs->poses_cls[l];
     }
-    h->m->forward_train(camera, lidar, status, noise, timesteps, target_traj, B, o, outs->loss, cls_weight, reg_weight,
-                        static_cast<hipStream_t>(stream));
+    KindScope ks(*h->m, d.kinds);
+    h->m->forward_train(d.cam, d.lid, in->status, in->noise, timesteps, target_traj, B, o, outs->loss, cls_weight,
+                        reg_weight, static_cast<hipStream_t>(stream));
   });
+}
+
+int dd_forward_train(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
+                     const int* timesteps, const float* target_traj, int B, float cls_weight, float reg_weight,
+                     const dd_train_outputs* outs, void* stream) {
+  const dd_inputs in = float_inputs(camera, lidar, status, noise);
+  return dd_forward_train_in(h, &in, timesteps, target_traj, B, cls_weight, reg_weight, outs, stream);
 }
 
 int dd_forward(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise, int B,

@@ -26,6 +26,9 @@
 //    one 16-B store per pooled pixel quad.
 //  * Persistent grid (two 4-wave workgroups per CU, 66 KB LDS each); the next tile's input patch is
 //    loaded into registers while the current tile's MFMAs run.
+//  * Input forms: the NHWC4 fp32 copy, the caller's NCHW fp32 tensor of 1..3 channels, or the uint8 values both
+//    features are made from (HWC camera image, planar LiDAR counts), widened through a 256-entry table while the patch
+//    is split into the LDS images (template parameter U8 below) - bit-identical to the float forms on the same values.
 // Bound: MFMA (f16x3 ceiling 833 TF): 49 x 4 x 64 x 2 = 25 KFLOP per stem pixel, 1.17 x recompute,
 // 224 / 196 K padding; HBM traffic = the input once (+ halo re-reads) + the pooled map.
 #include <type_traits>
@@ -74,6 +77,10 @@ static_assert(MPW * MSTEP == NMT, "the M tiles split evenly over the waves");
 constexpr int ILD = (IH * IW + NT - 1) / NT;       // input pixels per thread per tile
 constexpr int IMG_BYTES = IH * IP * 8;             // one fp16 input image
 constexpr int LDS_BYTES = 2 * IMG_BYTES + NMT * 32 * SOP * 4;
+// uint8 inputs (U8 forms): a 256-entry table of the byte's value already in the LDS images' format, one dword per
+// byte value (f16x3: fp16 hi | lo << 16 of the fp32 table entry, split as sp_split4 splits; bf16: the bf16 bits),
+// behind the stem tile
+constexpr int TAB_BYTES = 256 * 4;
 
 // One input channel (the LiDAR histogram, SRC_C = 1; opt-in, DDMI_STEM1=1, read per dispatch): K = 7 kh x 8 kw = 56 real taps (kw = 7 and kh = 7 zero) in 4 k16 steps instead of 14 over the
 // 4-channel pixels. A lane's 8 halves are 8 consecutive input columns of one row, which start at an even column 2 lx:
@@ -112,7 +119,13 @@ __device__ inline void sp_split4(const sp_f4 v, sp_h4& hi, sp_h4& lo) {
 // SRC_C = 0: the input is the NHWC image padded to 4 channels at `in`; SRC_C = 1..3: the reference's NCHW feature
 // tensor with SRC_C channels, whose address the kernel reads from *src (a device word the runtime sets per call
 // outside the captured graph), the missing channels zero - the same 4-channel pixels, without the transpose pass.
-template <int PREC, int SRC_C, int ONE = 0>
+// U8 (uint8 features read in place, the widening moved into the patch load): 1 = *src is the (B, H, W, 3) HWC byte
+// image (the camera as cv2 holds it; SRC_C = 3), 2 = the planar (B, SRC_C, H, W) byte tensor (the clipped LiDAR
+// counts). A byte's fp32 value is in[byte] (`in` is then the 256-entry fp32 table, not an image): the kernel turns the
+// table into the LDS images' format once (TAB_BYTES above), load_patch keeps a pixel's bytes packed in one dword
+// (bit 31 = inside the map) and store_patch looks them up - the same hi / lo (bf16) bits the float forms compute from
+// the same fp32 values, so everything from the LDS images on is shared and the results are bit-identical.
+template <int PREC, int SRC_C, int ONE = 0, int U8 = 0>
 __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restrict__ in, const float* const* src, int H,
                                                        int W, int Hs, int Ws,
                                                        int Hp, int Wp, const uint16_t* __restrict__ wh,
@@ -122,6 +135,7 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
                                                        float* __restrict__ out, unsigned* flags, int tiles_x,
                                                        int tiles_y, int ntiles) {
   static_assert(!ONE || SRC_C == 1, "the one-channel form reads a one-channel NCHW input");
+  static_assert(U8 == 0 || (U8 == 1 && SRC_C == 3) || (U8 == 2 && SRC_C >= 1), "uint8 forms: HWC x 3 or planar x 1..3");
   constexpr bool C1 = ONE;
   constexpr int KSN = C1 ? KS1 : KS;
   constexpr int IMGB = C1 ? IMG1_BYTES : IMG_BYTES;
@@ -129,10 +143,26 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
   char* in_hi = lds;
   char* in_lo = lds + IMGB;
   float* so = reinterpret_cast<float*>(lds + 2 * IMGB);
+  const uint32_t* tab = reinterpret_cast<const uint32_t*>(lds + 2 * IMGB + NMT * 32 * SOP * 4);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, hl = lane >> 5;
   const int nt = wave & 1, mg = wave >> 1;
   const int co = nt * 32 + li;
+  if constexpr (U8 != 0) {
+    for (int i = threadIdx.x; i < 256; i += NT) {
+      const float v = in[i];
+      uint32_t e;
+      if constexpr (PREC == 1) {
+        e = __builtin_bit_cast(uint16_t, (__bf16)v);
+      } else {
+        const _Float16 h = (_Float16)v;
+        const _Float16 l = (_Float16)(v - (float)h);
+        e = (uint32_t)__builtin_bit_cast(uint16_t, h) | ((uint32_t)__builtin_bit_cast(uint16_t, l) << 16);
+      }
+      const_cast<uint32_t*>(tab)[i] = e;
+    }
+    __syncthreads();
+  }
 
   // ---- loop-invariant B fragments of this wave's 32 channels (k = kh*28 + kw*4 + ci; one channel: k = kh*8 + kw)
   sp_h8 bh[KSN], bl[KSN];
@@ -183,14 +213,41 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
     py0 = (t2 % tiles_y) * PH;
     b = t2 / tiles_y;
   };
-  sp_f4 pre[C1 ? 1 : ILD];
-  float pre1[C1 ? ILD1 : 1];
+  sp_f4 pre[(C1 || U8) ? 1 : ILD];
+  float pre1[(C1 && !U8) ? ILD1 : 1];
+  uint32_t pre8[U8 ? (C1 ? ILD1 : ILD) : 1];  // a pixel's bytes, channel c at bits 8c.., bit 31 = inside the map
   const float* __restrict__ img = SRC_C ? *src : in;
+  const uint8_t* __restrict__ img8 = reinterpret_cast<const uint8_t*>(img);
   const int64_t plane = (int64_t)H * W;
   auto load_patch = [&](int t) {
     int b, py0, px0;
     tile_origin(t, b, py0, px0);
     const int iy0 = 4 * py0 - 5, ix0 = 4 * px0 - 5;
+    if constexpr (U8 != 0) {
+      // consecutive threads take consecutive pixels: the byte loads of a row's neighbours fall in the same lines
+      // (HWC: 3 B apart; planar: 1 B apart per plane); 64-bit byte offsets, no alignment assumed
+#pragma unroll
+      for (int i = 0; i < (C1 ? ILD1 : ILD); ++i) {
+        const int e = tid + NT * i;
+        const int r = e / IW, c = e - (e / IW) * IW;
+        const int iy = iy0 + r, ix = ix0 + c;
+        const bool ok = e < IH * IW && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
+        uint32_t v = 0u;
+        if (ok) {
+          if constexpr (U8 == 1) {
+            const uint8_t* p = img8 + (((int64_t)b * H + iy) * W + ix) * 3;
+            v = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | 0x80000000u;
+          } else {
+            const uint8_t* p = img8 + (int64_t)b * SRC_C * plane + (int64_t)iy * W + ix;
+            v = (uint32_t)p[0] | 0x80000000u;
+            if constexpr (SRC_C > 1) v |= (uint32_t)p[plane] << 8;
+            if constexpr (SRC_C > 2) v |= (uint32_t)p[2 * plane] << 16;
+          }
+        }
+        pre8[i] = v;
+      }
+      return;
+    }
     if constexpr (C1) {
 #pragma unroll
       for (int i = 0; i < ILD1; ++i) {
@@ -233,7 +290,11 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
         if (e < IH * IW) {
           const int r = e / IW, c = e - (e / IW) * IW;
           _Float16 h, l;
-          if constexpr (PREC == 1) {
+          if constexpr (U8 != 0) {
+            const uint32_t t0 = (pre8[i] >> 31) ? tab[pre8[i] & 255u] : 0u;
+            h = __builtin_bit_cast(_Float16, (uint16_t)(t0 & 0xffffu));
+            l = __builtin_bit_cast(_Float16, (uint16_t)(t0 >> 16));
+          } else if constexpr (PREC == 1) {
             h = __builtin_bit_cast(_Float16, __builtin_bit_cast(uint16_t, (__bf16)pre1[i]));
             l = (_Float16)0.f;
           } else {
@@ -258,7 +319,16 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
       const int e = tid + NT * i;
       if (e < IH * IW) {
         const int r = e / IW, c = e - (e / IW) * IW;
-        if constexpr (PREC == 1) {
+        if constexpr (U8 != 0) {
+          const uint32_t v = pre8[i];
+          uint32_t t0 = tab[v & 255u], t1 = 0u, t2 = 0u;
+          if constexpr (SRC_C > 1) t1 = tab[(v >> 8) & 255u];
+          if constexpr (SRC_C > 2) t2 = tab[(v >> 16) & 255u];
+          if (!(v >> 31)) t0 = t1 = t2 = 0u;  // outside the map: zero whatever the table holds for byte 0
+          *reinterpret_cast<uint2*>(in_hi + (r * IP + c) * 8) = make_uint2((t0 & 0xffffu) | (t1 << 16), t2 & 0xffffu);
+          if constexpr (PREC == 0)
+            *reinterpret_cast<uint2*>(in_lo + (r * IP + c) * 8) = make_uint2((t0 >> 16) | (t1 & 0xffff0000u), t2 >> 16);
+        } else if constexpr (PREC == 1) {
           *reinterpret_cast<sp_b4*>(in_hi + (r * IP + c) * 8) = __builtin_convertvector(pre[i], sp_b4);
         } else {
           sp_h4 hi, lo;
@@ -397,13 +467,15 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
 
 // Returns false when the conv is not a 7x7 / s2 / p3, Cin 4, Cout 64 f16x3 / bf16 stem on a contiguous
 // NHWC4 input (src == nullptr) or on the NCHW tensor of src_c channels whose address is the device word *src
-// (the caller then runs the conv and the pool separately).
-bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st, const float* const* src,
-                      int src_c) {
+// (the caller then runs the conv and the pool separately). u8 = 1 / 2: *src is the uint8 (B, H, W, 3) HWC image
+// (src_c 3) / the planar uint8 (B, src_c, H, W) tensor and lut the 256 fp32 values of the bytes (device memory).
+bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st, const void* const* src,
+                      int src_c, int u8, const float* lut) {
   if (!a.wh || (a.prec == 0 && !a.wl) || (a.prec != 0 && a.prec != 1) || !a.wsinv) return false;
   if (a.KH != 7 || a.KW != 7 || a.stride != 2 || a.pad != 3 || a.Cin != 4 || a.Cout != 64 || a.batch != 1 || a.res ||
       !a.relu)
     return false;
+  if (u8 < 0 || u8 > 2 || (u8 && (!src || !lut)) || (u8 == 1 && src_c != 3)) return false;
   if (src) {
     if (src_c < 1 || src_c > 3 || (int64_t)a.Nimg * src_c * a.H * a.W >= (int64_t(1) << 31)) return false;
   } else if (a.in_sw != 4 || a.in_sh != (int64_t)a.W * 4 || a.in_sn != (int64_t)a.H * a.W * 4) {
@@ -427,15 +499,30 @@ bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStr
   const int c = src ? src_c : 0;
   const char* oe = getenv("DDMI_STEM1");
   const bool one = c == 1 && oe && atoi(oe) != 0;
-  static std::atomic<uint64_t> attr[2][5];
+  static std::atomic<uint64_t> attr[2][3][5];
   auto go = [&](auto kern, int c) {
-    const int lds = (c == 1 && one) ? LDS1_BYTES : LDS_BYTES;
-    set_max_lds_once(attr[a.prec][c == 1 && one ? 4 : c], reinterpret_cast<const void*>(kern), lds);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, a.in, src, a.H, a.W, Hs, Ws, Hp, Wp, a.wh, a.wl,
+    const int lds = ((c == 1 && one) ? LDS1_BYTES : LDS_BYTES) + (u8 ? TAB_BYTES : 0);
+    set_max_lds_once(attr[a.prec][u8][c == 1 && one ? 4 : c], reinterpret_cast<const void*>(kern), lds);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, u8 ? lut : a.in,
+                       reinterpret_cast<const float* const*>(src), a.H, a.W, Hs, Ws, Hp, Wp, a.wh, a.wl,
                        (int)a.ldh, a.wsinv, a.bias, a.alpha, pool_out, a.flags, tiles_x, tiles_y, ntiles);
   };
   auto pick = [&](auto PR) {
     constexpr int P = decltype(PR)::value;
+    if (u8 == 1) {
+      go(stem_pool_kernel<P, 3, 0, 1>, 3);
+      return;
+    }
+    if (u8 == 2) {
+      switch (c) {
+        case 1:
+          if (one) go(stem_pool_kernel<P, 1, 1, 2>, 1); else go(stem_pool_kernel<P, 1, 0, 2>, 1);
+          break;
+        case 2: go(stem_pool_kernel<P, 2, 0, 2>, 2); break;
+        default: go(stem_pool_kernel<P, 3, 0, 2>, 3); break;
+      }
+      return;
+    }
     switch (c) {
       case 1:
         if (one) go(stem_pool_kernel<P, 1, 1>, 1); else go(stem_pool_kernel<P, 1, 0>, 1);

@@ -12,6 +12,12 @@ works end to end on an ``AgentInput``, with the per-pixel / per-point work in HI
   splat (``np.histogramdd`` semantics, bit-exact; tests/golden/lidar_feat_*.npz).
 * status: [driving_command (4), ego_velocity (2), ego_acceleration (2)] (:46-53), 8 floats.
 
+Both sensor features are byte-valued by construction (camera k / 255, LiDAR min(c, hist_max) / hist_max), and the
+forward takes them as those bytes (include/ddmi.h, dd_inputs): ``dtype=torch.uint8`` makes the builders write the
+(B, H, W, 3) HWC resized image and the (B, C, 256, 256) clipped counts instead of the floats (a quarter of the bytes,
+bit-identical forward), and ``quantize_features`` turns a float feature dict into that form - or refuses, if a value is
+not exactly byte-valued.
+
 Features are returned as DEVICE tensors (the forward consumes them in place). There is no CPU
 fallback: without libddmi.so or a GPU this raises. The CPU restatement used to check it lives in
 ``oracle/features.py`` (test infrastructure).
@@ -126,9 +132,64 @@ def _device(device: Optional[int]) -> torch.device:
     return torch.device(f"cuda:{torch.cuda.current_device() if device is None else int(device)}")
 
 
+def _check_dtype(dtype):
+    if dtype not in (torch.float32, torch.uint8):
+        raise ValueError(f"feature dtype must be torch.float32 or torch.uint8, got {dtype!r}")
+    return dtype == torch.uint8
+
+
+def widen_features(features: Dict[str, torch.Tensor], cfg: TransfuserConfig) -> Dict[str, torch.Tensor]:
+    """The float features a uint8 feature dict stands for, in the reference's layouts: camera (B, H, W, 3) bytes ->
+    (B, 3, H, W) ``k / 255``, LiDAR counts -> ``min(c, hist_max) / hist_max`` (float64 division rounded to float32,
+    as the reference's numpy does). Float entries pass through. Pure torch: works without a GPU."""
+    out = dict(features)
+    cam, lid = torch.as_tensor(features["camera_feature"]), torch.as_tensor(features["lidar_feature"])
+    if cam.dtype == torch.uint8:
+        out["camera_feature"] = cam.permute(0, 3, 1, 2).float().div(255).contiguous()
+    if lid.dtype == torch.uint8:
+        hm = int(cfg.hist_max_per_pixel)
+        out["lidar_feature"] = (lid.clamp(max=hm).double() / hm).float()
+    return out
+
+
+def quantize_features(features: Dict[str, torch.Tensor], cfg: TransfuserConfig) -> Dict[str, torch.Tensor]:
+    """The uint8 form of a float feature dict: ``camera_feature`` (B, 3, H, W) -> (B, H, W, 3) bytes k with
+    ``k / 255 == value``, ``lidar_feature`` -> the counts c with ``c / hist_max_per_pixel == value``; the other entries
+    pass through, as do features that are uint8 already. Exact or not at all: a value that is not bit-equal to its
+    byte's float raises ValueError naming the first offending element - nothing is ever rounded silently, so
+    ``widen_features(quantize_features(x)) == x`` bitwise. Pure torch: works without a GPU."""
+    hm = int(cfg.hist_max_per_pixel)
+    if not 1 <= hm <= 255:
+        raise ValueError(f"uint8 LiDAR features need hist_max_per_pixel in 1..255, got {hm}")
+    out = dict(features)
+
+    def exact(name, x, scale, back):
+        x = torch.as_tensor(x)
+        if x.dtype == torch.uint8:
+            return x, None
+        x = x.float()
+        q = (x.double() * scale).round().clamp(0, scale)
+        q = torch.where(torch.isfinite(q), q, torch.zeros_like(q)).to(torch.uint8)
+        bad = (back(q) != x).reshape(-1)  # NaN, out of range and off-grid values all differ from their byte's float
+        if bool(bad.any()):
+            i = int(torch.nonzero(bad)[0])
+            idx = tuple(int(v) for v in np.unravel_index(i, tuple(x.shape)))
+            raise ValueError(f"{name}{list(idx)} = {float(x.reshape(-1)[i])!r} is not k / {scale} for an integer k in "
+                             f"0..{scale}: the feature is not byte-valued and cannot be passed as uint8")
+        return q, x
+
+    cam, was = exact("camera_feature", features["camera_feature"], 255, lambda q: q.float().div(255))
+    out["camera_feature"] = cam.permute(0, 2, 3, 1).contiguous() if was is not None else cam
+    lid, _ = exact("lidar_feature", features["lidar_feature"], hm, lambda q: (q.double() / hm).float())
+    out["lidar_feature"] = lid
+    return out
+
+
 def camera_features(images: Sequence[Sequence[np.ndarray]], cfg: TransfuserConfig,
-                    device: Optional[int] = None) -> torch.Tensor:
-    """images: per scene (cam_l0, cam_f0, cam_r0) uint8 HWC arrays -> (B, 3, H, W) float on the GPU."""
+                    device: Optional[int] = None, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """images: per scene (cam_l0, cam_f0, cam_r0) uint8 HWC arrays -> (B, 3, H, W) float on the GPU, or with
+    ``dtype=torch.uint8`` the (B, H, W, 3) resized image itself (the float form is it / 255)."""
+    u8 = _check_dtype(dtype)
     lib = _lib.load()
     dev = _device(device)
     B = len(images)
@@ -145,18 +206,25 @@ def camera_features(images: Sequence[Sequence[np.ndarray]], cfg: TransfuserConfi
         arr = stage.numpy().reshape(B, 3, h, w, 3)
         cams = _upload_chunked(dev, "camera", stage, (B, 3, h, w, 3), 3 * B,
                                lambda bc: np.copyto(arr[bc // 3, bc % 3], images[bc // 3][bc % 3]))
-    out = torch.empty((B, 3, cfg.camera_height, cfg.camera_width), device=dev)
+    if u8:
+        out = torch.empty((B, cfg.camera_height, cfg.camera_width, 3), device=dev, dtype=torch.uint8)
+    else:
+        out = torch.empty((B, 3, cfg.camera_height, cfg.camera_width), device=dev)
     s = torch.cuda.current_stream(dev)
-    _lib.check(lib.dd_build_camera(cams.data_ptr(), B, h, w, out.data_ptr(), cfg.camera_height, cfg.camera_width,
-                                   s.cuda_stream), lib, op=True)
+    build = lib.dd_build_camera_u8 if u8 else lib.dd_build_camera
+    _lib.check(build(cams.data_ptr(), B, h, w, out.data_ptr(), cfg.camera_height, cfg.camera_width,
+                     s.cuda_stream), lib, op=True)
     out.record_stream(s)
     cams.record_stream(s)
     return out
 
 
-def lidar_features(points: Sequence[np.ndarray], cfg: TransfuserConfig, device: Optional[int] = None) -> torch.Tensor:
+def lidar_features(points: Sequence[np.ndarray], cfg: TransfuserConfig, device: Optional[int] = None,
+                   dtype: torch.dtype = torch.float32) -> torch.Tensor:
     """points: per scene a (3, N) float32 planar xyz array (NAVSIM ``lidar_pc[:3]``) ->
-    (B, C, 256, 256) float on the GPU."""
+    (B, C, 256, 256) float on the GPU, or with ``dtype=torch.uint8`` the clipped counts min(c, hist_max_per_pixel)
+    (the float form is them / hist_max_per_pixel)."""
+    u8 = _check_dtype(dtype)
     lib = _lib.load()
     dev = _device(device)
     B = len(points)
@@ -175,13 +243,14 @@ def lidar_features(points: Sequence[np.ndarray], cfg: TransfuserConfig, device: 
     res = cfg.lidar_resolution_height
     if cfg.lidar_resolution_width != res:
         raise ValueError("lidar feature: square BEV grid expected")
-    out = torch.empty((B, C, res, res), device=dev)
+    out = torch.empty((B, C, res, res), device=dev, dtype=torch.uint8 if u8 else torch.float32)
     s = torch.cuda.current_stream(dev)
-    _lib.check(lib.dd_build_lidar(xyz_d.data_ptr() if xyz_d.numel() else None, offs_d.data_ptr(), B, C,
-                                  out.data_ptr(), res, float(cfg.lidar_min_x), float(cfg.lidar_max_x),
-                                  int(cfg.pixels_per_meter), float(cfg.max_height_lidar),
-                                  float(cfg.lidar_split_height), int(cfg.hist_max_per_pixel),
-                                  int(counts.max()) if B else 0, s.cuda_stream), lib, op=True)
+    build = lib.dd_build_lidar_u8 if u8 else lib.dd_build_lidar
+    _lib.check(build(xyz_d.data_ptr() if xyz_d.numel() else None, offs_d.data_ptr(), B, C,
+                     out.data_ptr(), res, float(cfg.lidar_min_x), float(cfg.lidar_max_x),
+                     int(cfg.pixels_per_meter), float(cfg.max_height_lidar),
+                     float(cfg.lidar_split_height), int(cfg.hist_max_per_pixel),
+                     int(counts.max()) if B else 0, s.cuda_stream), lib, op=True)
     out.record_stream(s)
     xyz_d.record_stream(s)
     offs_d.record_stream(s)
@@ -199,9 +268,13 @@ def status_features(egos: Sequence, device: Optional[int] = None) -> torch.Tenso
 class TransfuserFeatureBuilder:
     """transfuser_features.py:25-55 (inference features only), computed on the GPU."""
 
-    def __init__(self, config: TransfuserConfig, device: Optional[int] = None):
+    def __init__(self, config: TransfuserConfig, device: Optional[int] = None, dtype: torch.dtype = torch.float32):
+        """``dtype=torch.uint8``: the camera / LiDAR features as bytes ((B,H,W,3) image, (B,C,256,256) counts), which
+        the forward reads in place."""
+        _check_dtype(dtype)
         self._config = config
         self._device = device
+        self._dtype = dtype
 
     def get_unique_name(self) -> str:
         return "transfuser_feature"
@@ -217,7 +290,7 @@ class TransfuserFeatureBuilder:
                 for a in agent_inputs]
         pcs = [a.lidars[-1].lidar_pc[0:3] for a in agent_inputs]  # LidarIndex.POSITION (x, y, z)
         return {
-            "camera_feature": camera_features(cams, self._config, self._device),
-            "lidar_feature": lidar_features(pcs, self._config, self._device),
+            "camera_feature": camera_features(cams, self._config, self._device, dtype=self._dtype),
+            "lidar_feature": lidar_features(pcs, self._config, self._device, dtype=self._dtype),
             "status_feature": status_features([a.ego_statuses[-1] for a in agent_inputs], self._device),
         }

@@ -2,7 +2,9 @@
 
 ``DiffusionDriveModel.forward(features)`` has the reference's contract
 (transfuser_model_v2.py:98-162, eval mode): a feature dict with ``camera_feature``
-(B,3,256,1024), ``lidar_feature`` (B,1,256,256), ``status_feature`` (B,8) in, a dict with
+(B,3,256,1024), ``lidar_feature`` (B,1,256,256), ``status_feature`` (B,8) in (either sensor feature may instead be
+the ``torch.uint8`` tensor it is made from: the (B,256,1024,3) HWC resized image, the (B,C,256,256) clipped histogram
+counts; the stems widen the bytes in place and the result is bit-identical), a dict with
 ``trajectory`` (B,8,3) out (plus ``bev_semantic_map`` / ``agent_states`` / ``agent_labels`` when
 ``heads=True``). The forward runs entirely in ``libddmi.so`` on the GPU; PyTorch only provides
 device memory and the stream. There is no CPU fallback: without the library or a GPU it raises.
@@ -144,6 +146,32 @@ class DiffusionDriveModel:
         t = torch.as_tensor(t)
         return t.to(device=f"cuda:{self.device}", dtype=dtype).contiguous()
 
+    def _sensor_inputs(self, features, B: int):
+        """The camera / LiDAR features on the device, shape-checked, and the dd_inputs descriptor naming them. A
+        ``torch.uint8`` camera is the (B, H, W, 3) HWC resized image (byte k = k / 255), a ``torch.uint8`` LiDAR the
+        planar (B, C, H, W) histogram counts (byte c = min(c, hist_max_per_pixel) / hist_max_per_pixel); any other
+        dtype is taken as float32 in the reference's layouts. The two kinds are independent."""
+        cfg = self.config
+        cam, lid = torch.as_tensor(features["camera_feature"]), torch.as_tensor(features["lidar_feature"])
+        cam_u8, lid_u8 = cam.dtype == torch.uint8, lid.dtype == torch.uint8
+        cam_shape = (B, cfg.camera_height, cfg.camera_width, 3) if cam_u8 else (B, 3, cfg.camera_height, cfg.camera_width)
+        lid_shape = (B, cfg.lidar_in_channels, cfg.lidar_resolution_height, cfg.lidar_resolution_width)
+        if tuple(cam.shape) != cam_shape:
+            what = f"a uint8 camera_feature must be HWC (B,{cam_shape[1]},{cam_shape[2]},3)" if cam_u8 else \
+                f"camera_feature must be (B,3,{cfg.camera_height},{cfg.camera_width})"
+            raise ValueError(f"{what}, got {tuple(cam.shape)}")
+        if tuple(lid.shape) != lid_shape:
+            raise ValueError(f"lidar_feature has shape {tuple(lid.shape)}, expected {lid_shape}")
+        if lid_u8 and not 1 <= int(cfg.hist_max_per_pixel) <= 255:
+            raise ValueError(f"a uint8 lidar_feature needs hist_max_per_pixel in 1..255, got {cfg.hist_max_per_pixel}")
+        cam = self._dev(cam, dtype=torch.uint8 if cam_u8 else torch.float32)
+        lid = self._dev(lid, dtype=torch.uint8 if lid_u8 else torch.float32)
+        ins = _lib.DDInputs()
+        setattr(ins, "camera_u8" if cam_u8 else "camera_f32", cam.data_ptr())
+        setattr(ins, "lidar_u8" if lid_u8 else "lidar_f32", lid.data_ptr())
+        ins.lidar_hist_max = int(cfg.hist_max_per_pixel) if lid_u8 else 0
+        return cam, lid, ins
+
     def forward(self, features: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None,
                 steps: Optional[int] = None, heads: bool = False, modes: bool = False,
                 stream: Optional[torch.cuda.Stream] = None, safe: bool = False) -> Dict[str, torch.Tensor]:
@@ -201,17 +229,13 @@ class DiffusionDriveModel:
         cfg = self.config
         cam = features["camera_feature"]
         out_device = cam.device if isinstance(cam, torch.Tensor) else torch.device("cpu")
-        cam = self._dev(cam)
-        lid = self._dev(features["lidar_feature"])
         st = self._dev(features["status_feature"])
         B = st.shape[0]
         Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
-        if tuple(cam.shape) != (B, 3, cfg.camera_height, cfg.camera_width):
-            raise ValueError(f"camera_feature must be (B,3,{cfg.camera_height},{cfg.camera_width}), got {tuple(cam.shape)}")
-        if tuple(lid.shape) != (B, cfg.lidar_in_channels, cfg.lidar_resolution_height, cfg.lidar_resolution_width):
-            raise ValueError(f"lidar_feature has shape {tuple(lid.shape)}")
+        cam, lid, ins = self._sensor_inputs(features, B)
         if tuple(st.shape) != (B, 8):
             raise ValueError(f"status_feature must be (B,8), got {tuple(st.shape)}")
+        ins.status = st.data_ptr()
         if noise is None:
             # the reference draws its DDIM start noise here (transfuser_model_v2.py:593), on CPU
             noise = torch.randn((B, Q, P, 2))
@@ -247,10 +271,9 @@ class DiffusionDriveModel:
             outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
             outs.agent_states = res["agent_states"].data_ptr()
             outs.agent_labels = res["agent_labels"].data_ptr()
-        _lib.check(self.lib.dd_forward_ex(self.handle, cam.data_ptr(), lid.data_ptr(), st.data_ptr(),
-                                          nz.data_ptr() if nz is not None else None,
-                                          B, int(steps or cfg.denoise_steps), ctypes.byref(outs),
-                                          s.cuda_stream), self.lib)
+        ins.noise = nz.data_ptr() if nz is not None else None
+        _lib.check(self.lib.dd_forward_in(self.handle, ctypes.byref(ins), B, int(steps or cfg.denoise_steps),
+                                          ctypes.byref(outs), s.cuda_stream), self.lib)
         if out_device.type != "cuda":
             res = {k: v.to(out_device) for k, v in res.items()}
         return res
@@ -293,17 +316,13 @@ class DiffusionDriveModel:
         cfg = self.config
         cam = features["camera_feature"]
         out_device = cam.device if isinstance(cam, torch.Tensor) else torch.device("cpu")
-        cam = self._dev(cam)
-        lid = self._dev(features["lidar_feature"])
         st = self._dev(features["status_feature"])
         B = st.shape[0]
         Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
-        if tuple(cam.shape) != (B, 3, cfg.camera_height, cfg.camera_width):
-            raise ValueError(f"camera_feature must be (B,3,{cfg.camera_height},{cfg.camera_width}), got {tuple(cam.shape)}")
-        if tuple(lid.shape) != (B, cfg.lidar_in_channels, cfg.lidar_resolution_height, cfg.lidar_resolution_width):
-            raise ValueError(f"lidar_feature has shape {tuple(lid.shape)}")
+        cam, lid, ins = self._sensor_inputs(features, B)
         if tuple(st.shape) != (B, 8):
             raise ValueError(f"status_feature must be (B,8), got {tuple(st.shape)}")
+        ins.status = st.data_ptr()
         nz = None if isinstance(noise, str) else self._dev(noise)
         # as _forward_on: the caller may drop its tensors while stream s still reads them
         for t in (cam, lid, st, nz):
@@ -331,9 +350,9 @@ class DiffusionDriveModel:
             outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
             outs.agent_states = res["agent_states"].data_ptr()
             outs.agent_labels = res["agent_labels"].data_ptr()
-        _lib.check(self.lib.dd_forward_samples(self.handle, cam.data_ptr(), lid.data_ptr(), st.data_ptr(),
-                                               nz.data_ptr() if nz is not None else None, B, S,
-                                               int(steps or cfg.denoise_steps), ctypes.byref(outs), s.cuda_stream),
+        ins.noise = nz.data_ptr() if nz is not None else None
+        _lib.check(self.lib.dd_forward_samples_in(self.handle, ctypes.byref(ins), B, S,
+                                                  int(steps or cfg.denoise_steps), ctypes.byref(outs), s.cuda_stream),
                    self.lib)
         if out_device.type != "cuda":
             res = {k: v.to(out_device) for k, v in res.items()}
@@ -391,8 +410,7 @@ class DiffusionDriveModel:
         B = torch.as_tensor(features["status_feature"]).shape[0]
         Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
         with torch.cuda.stream(s):
-            cam = self._dev(features["camera_feature"])
-            lid = self._dev(features["lidar_feature"])
+            cam, lid, ins = self._sensor_inputs(features, B)
             st = self._dev(features["status_feature"])
             nz = self._dev(noise)
             tt = self._dev(timesteps, dtype=torch.int32)
@@ -426,10 +444,11 @@ class DiffusionDriveModel:
                 outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
                 outs.agent_states = res["agent_states"].data_ptr()
                 outs.agent_labels = res["agent_labels"].data_ptr()
-            _lib.check(self.lib.dd_forward_train(self.handle, cam.data_ptr(), lid.data_ptr(), st.data_ptr(),
-                                                 nz.data_ptr(), tt.data_ptr(), tg.data_ptr() if tg is not None else None,
-                                                 B, float(cfg.trajectory_cls_weight), float(cfg.trajectory_reg_weight),
-                                                 ctypes.byref(outs), s.cuda_stream), self.lib)
+            ins.status, ins.noise = st.data_ptr(), nz.data_ptr()
+            _lib.check(self.lib.dd_forward_train_in(self.handle, ctypes.byref(ins), tt.data_ptr(),
+                                                    tg.data_ptr() if tg is not None else None, B,
+                                                    float(cfg.trajectory_cls_weight), float(cfg.trajectory_reg_weight),
+                                                    ctypes.byref(outs), s.cuda_stream), self.lib)
         if s != cur:
             # the outputs (the loss reduction last) were written on s: order the caller's stream after it, so a
             # .cpu() / .item() on the current stream reads finished values

@@ -38,7 +38,9 @@ from .features import TransfuserFeatureBuilder
 
 class BatchedTrajectoryRunner:
     def __init__(self, agent: DiffusionDriveAgent, batch_size: int = 64, device: Optional[int] = None,
-                 lanes: int = 1):
+                 lanes: int = 1, feature_dtype: torch.dtype = torch.float32):
+        """``feature_dtype=torch.uint8``: the GPU feature builder writes the camera / LiDAR features as bytes and the
+        forward reads them in place (a quarter of the feature bytes, bit-identical trajectories)."""
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         if lanes < 1:
@@ -48,7 +50,7 @@ class BatchedTrajectoryRunner:
         self.lanes = lanes
         self._clones: List = []
         self.device = agent._transfuser_model.device if device is None else device
-        self.builder = TransfuserFeatureBuilder(agent._config, device=self.device)
+        self.builder = TransfuserFeatureBuilder(agent._config, device=self.device, dtype=feature_dtype)
         self.failed: List[Tuple[str, str]] = []
 
     def _features(self, inputs: List):

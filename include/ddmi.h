@@ -16,6 +16,10 @@
  *   dd_forward_samples  S draws of the same forward's trajectory distribution per scene (S start noises through
  *                  TrajectoryHead.forward_test, transfuser_model_v2.py:578-641) over ONE pass of everything before
  *                  the head; the reference would run its whole forward once per draw
+ *   dd_forward_in / dd_forward_samples_in / dd_forward_train_in  the same three forwards with the inputs in a
+ *                  dd_inputs descriptor, which also takes the camera / LiDAR features as the uint8 values they are
+ *                  made from (no reference counterpart: the reference widens them to float on the CPU,
+ *                  transfuser_features.py:57-138)
  *   dd_destroy  <- agent teardown (no reference counterpart; frees device memory)
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
@@ -94,6 +98,34 @@ typedef struct dd_train_outputs {
   float* agent_labels;     /* B x 30 */
 } dd_train_outputs;
 
+/* Inputs of dd_forward_in / dd_forward_samples_in / dd_forward_train_in (device pointers). Both sensor features are
+ * byte-valued by construction, and either may be passed as the bytes instead of the floats - independently of the
+ * other; the fused stems then widen the bytes in their patch load (exactly: the stems see the same fp32 values, so
+ * the result is bit-identical to the float call's) and the feature never exists as floats in memory:
+ *   camera_f32  (B, 3, cam_h, cam_w) fp32 NCHW, or
+ *   camera_u8   (B, cam_h, cam_w, 3) uint8 HWC - the resized image as cv2 / NAVSIM hold it before ToTensor
+ *               (transfuser_features.py:57-77); byte k stands for float(k) / 255.0f (correctly rounded: torch's
+ *               uint8 -> .float().div(255), and what dd_build_camera writes);
+ *   lidar_f32   (B, C, lidar_h, lidar_w) fp32, or
+ *   lidar_u8    (B, C, lidar_h, lidar_w) uint8 histogram counts, planar like the float tensor; byte c stands for
+ *               (float)((double)min(c, lidar_hist_max) / (double)lidar_hist_max) (transfuser_features.py:133-137;
+ *               counts above lidar_hist_max are clipped, so raw or clipped counts give the same result);
+ *   lidar_hist_max  1..255, read only with lidar_u8 (the reference's hist_max_per_pixel, 5); may change from call
+ *               to call on one handle.
+ * Exactly one pointer per sensor: both or neither set, or a lidar_hist_max outside 1..255 with lidar_u8, returns
+ * DD_ERR_INVALID before any device work with the field's name in dd_last_error(). No alignment is required of the
+ * uint8 tensors. A uint8 call and a float call at the same shape are two captured programs of the handle; either
+ * may follow the other. */
+typedef struct dd_inputs {
+  const float* camera_f32;
+  const uint8_t* camera_u8;
+  const float* lidar_f32;
+  const uint8_t* lidar_u8;
+  int lidar_hist_max;
+  const float* status;     /* B x 8, as dd_forward_ex */
+  const float* noise;      /* as the float entry point's noise (nullable where that one's is) */
+} dd_inputs;
+
 /* Fill *cfg with the reference defaults. */
 void dd_default_config(dd_config* cfg);
 
@@ -116,6 +148,10 @@ int dd_forward(dd_handle* h, const float* camera, const float* lidar, const floa
 int dd_forward_ex(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
                   int B, int steps, const dd_outputs* outs, void* stream);
 
+/* dd_forward_ex with the inputs in a descriptor (fp32 or uint8 features, dd_inputs above). dd_forward_ex is this call
+ * with camera_f32 / lidar_f32 set. */
+int dd_forward_in(dd_handle* h, const dd_inputs* in, int B, int steps, const dd_outputs* outs, void* stream);
+
 /* S trajectory samples per scene from one perception pass. The planner is a diffusion model: one start noise draws
  * one trajectory from its output distribution, and everything before the trajectory head (trunks, GPT fusion, FPN,
  * bev_proj, the tf decoder and its hoists, the optional heads: ~93 % of a forward) does not depend on the noise. This
@@ -134,6 +170,10 @@ int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, co
                        const float* noise /* B x S x Q x P x 2, or NULL */, int B, int S, int steps,
                        const dd_sample_outputs* outs, void* stream);
 
+/* dd_forward_samples with the inputs in a descriptor (in->noise: B x S x Q x P x 2, or NULL). */
+int dd_forward_samples_in(dd_handle* h, const dd_inputs* in, int B, int S, int steps, const dd_sample_outputs* outs,
+                          void* stream);
+
 /* The training-mode trajectory head over the eval-mode network, as a loss evaluator: replaces
  * V2TransfuserModel.forward(features, targets) with TrajectoryHead.forward_train (transfuser_model_v2.py:520-576) and
  * LossComputer (modules/multimodal_loss.py:119-168). forward_train's two random draws are inputs: timesteps (B
@@ -146,6 +186,9 @@ int dd_forward_samples(dd_handle* h, const float* camera, const float* lidar, co
 int dd_forward_train(dd_handle* h, const float* camera, const float* lidar, const float* status, const float* noise,
                      const int* timesteps, const float* target_traj, int B, float cls_weight, float reg_weight,
                      const dd_train_outputs* outs, void* stream);
+/* dd_forward_train with the inputs in a descriptor (in->noise required). */
+int dd_forward_train_in(dd_handle* h, const dd_inputs* in, const int* timesteps, const float* target_traj, int B,
+                        float cls_weight, float reg_weight, const dd_train_outputs* outs, void* stream);
 /* The BEV-semantic term of the training loss, transfuser_loss.py:28-29 (F.cross_entropy(bev_semantic_map,
  * target.long()), mean over every pixel): logits (B,C,H,W) NCHW and target (B,H,W) uint8 class ids in device memory,
  * work = dd_bev_semantic_loss_work(B, H, W) floats of device scratch, loss = one device float. Deterministic (fixed
@@ -177,7 +220,8 @@ int dd_reset_stats(dd_handle* h);
  * launches and algorithmic FLOPs (conv_gemm) since the last reset. Synchronises pending events. */
 int dd_kernel_stats(dd_handle* h, const char* kernel, double* total_ms, long long* launches, double* flops);
 /* Algorithmic HBM bytes of the same launches (conv / GEMM classes: input map, output, residual and weight
- * image each counted once; 0 for the other classes). */
+ * image each counted once; "stem_pool": the input at its element size - 4 B per fp32 element, 1 B per uint8
+ * element - the pooled map and the weight image; 0 for the other classes). */
 int dd_kernel_bytes(dd_handle* h, const char* kernel, double* bytes);
 /* Enable / disable hipGraph capture + replay of the forward (default on). */
 int dd_set_graph(dd_handle* h, int enable);
@@ -262,6 +306,16 @@ int dd_build_lidar(const float* xyz, const int64_t* offsets, int B, int channels
                    float range_lo, float range_hi, int pixels_per_meter, float max_height, float split_height,
                    int hist_max, long long max_points, void* stream);
 
+/* The same two features as bytes, for dd_inputs.camera_u8 / lidar_u8 (same arguments as the float forms): out =
+ * device uint8 (B, out_h, out_w, 3) HWC, the resized image itself ((s + 2) >> 2 of the four taps; the float form is
+ * this / 255), and device uint8 (B, channels, res, res) = min(count, hist_max) (hist_max in 1..255; the float form
+ * is this / hist_max; out 4-byte aligned). */
+int dd_build_camera_u8(const uint8_t* cams, int B, int src_h, int src_w, uint8_t* out, int out_h, int out_w,
+                       void* stream);
+int dd_build_lidar_u8(const float* xyz, const int64_t* offsets, int B, int channels, uint8_t* out, int resolution,
+                      float range_lo, float range_hi, int pixels_per_meter, float max_height, float split_height,
+                      int hist_max, long long max_points, void* stream);
+
 /* ---- single-op entry points (parity tests of individual kernels) ---------------------------- */
 /* Last error message of a dd_op_* call on the calling thread. */
 const char* dd_op_last_error(void);
@@ -299,6 +353,11 @@ int dd_op_stem_pool(const float* in, int B, int H, int W, const float* wgt, cons
  * which runs a one-channel kernel form: 4 k16 steps instead of 14). */
 int dd_op_stem_pool_nchw(const float* in, int B, int C, int H, int W, const float* wgt, const float* bias, float* out,
                          int prec, unsigned* flags, void* stream);
+/* The same on uint8 features read in place (the forms dd_forward_in takes): layout 0 = in is (B, H, W, 3) HWC
+ * (C = 3), 1 = planar (B, C, H, W), C = 1..3; byte k stands for the fp32 value lut[k] (256 device floats). Equals
+ * dd_op_stem_pool_nchw on the widened NCHW tensor bit for bit. */
+int dd_op_stem_pool_u8(const uint8_t* in, int layout, int B, int C, int H, int W, const float* lut, const float* wgt,
+                       const float* bias, float* out, int prec, unsigned* flags, void* stream);
 /* C (M,N) = A (M,K) . W(N,K)^T [+ bias] [+ res (M,N)] [relu] */
 int dd_op_gemm(const float* A, int M, int K, const float* W, const float* bias, const float* res, float* C, int N,
                int relu, void* stream);
