@@ -116,6 +116,10 @@ constexpr unsigned DD_NUM_SYNC_TIMEOUT = 2u;  // a megakernel's inter-workgroup 
 // earlier arrivals than its barrier allows): the waits it guards cannot be trusted; dd_numerics_flags' clear re-zeroes
 // the counters
 constexpr unsigned DD_NUM_SYNC_STATE = 4u;
+// Largest exponent e of the f16x3 weight split's row scale s_r = 2^e (prep_split, pack_mk_weights): 2^126 and
+// 2^-126 are both normal fp32 numbers. A row with max|w_r| < 2^-112 would need more (2^128 = inf below 2^-113, a
+// subnormal 1 / s_r at 2^-113); it is scaled by 2^126 and keeps fewer bits, at less than 2^-150 per product.
+constexpr int kSplitMaxExp = 126;
 
 #ifdef __HIPCC__
 // Implicit-GEMM epilogue row table: element offsets of output / residual row m0 + r (r < BM) of a tile,

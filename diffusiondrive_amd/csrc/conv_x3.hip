@@ -12,6 +12,10 @@
 //
 // Range: weights are pre-split on the host with a per-output-channel power-of-two scale that puts
 // max|w| at 2^15 (exact; undone in the epilogue), so no weight lo part is lost to fp16 subnormals.
+// The scale's exponent stops at 126 (common.h kSplitMaxExp): a row with max|w| < 2^-112 - a channel
+// whose folded BatchNorm gamma has decayed to nothing - is scaled by 2^126, so that the scale and its
+// inverse stay normal fp32 numbers; it fills less of fp16's range, at < 2^-150 per unit activation.
+// An all-zero row keeps scale 1. Both rows then yield the bias, as fp32 does.
 // Activations are split unscaled: an |x| >= 65504 overflows its fp16 hi part, which makes every
 // output it feeds non-finite; the epilogue ORs DD_NUM_F16_OVERFLOW into *flags for any non-finite
 // accumulator (the runtime reports it via dd_numerics_flags; the host raises / re-runs in fp32). Activations below 2^-3 have a subnormal lo part: absolute error

@@ -798,7 +798,7 @@ void pack_mk_weights(const float* w, int nout, int nin, std::vector<_Float16>& p
     if (amax > 0.f && std::isfinite(amax)) {
       int ex;
       std::frexp(amax, &ex);
-      e = 15 - ex;
+      e = std::min(15 - ex, kSplitMaxExp);  // as prep_split
     }
     scale[r] = std::ldexp(1.0f, e);
     sinv[r] = std::ldexp(1.0f, -e);

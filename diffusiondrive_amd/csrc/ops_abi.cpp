@@ -1,6 +1,7 @@
 // Single-kernel C-ABI entry points (include/ddmi.h, "single-op entry points"): used by the GPU
 // parity tests to check each kernel in isolation against PyTorch-CPU fp32 on the same inputs.
 #include <cmath>
+#include <cstring>
 #include <string>
 
 #include "../../include/ddmi.h"
@@ -35,6 +36,33 @@ extern "C" {
 const char* dd_op_last_error(void) { return g_op_err.c_str(); }
 
 const char* dd_op_last_kernel(void) { return last_conv_config(); }
+
+int dd_op_split_weights(const float* w, int rows, int K, uint16_t* hi, uint16_t* lo, uint16_t* b16, float* sinv,
+                        int* ldh_out) {
+  return op_guard([&] {
+    if (!w || rows < 1 || K < 1) throw std::invalid_argument("dd_op_split_weights: null pointer or bad shape");
+    Arena ar;  // host side only: never uploaded
+    const SplitW x = prep_split(ar, w, rows, K);
+    const size_t bytes = (size_t)rows * x.ldh * sizeof(uint16_t);
+    if (hi) std::memcpy(hi, ar.host(x.hi), bytes);
+    if (lo) std::memcpy(lo, ar.host(x.lo), bytes);
+    if (b16) std::memcpy(b16, ar.host(x.b16), bytes);
+    if (sinv) std::memcpy(sinv, ar.host(x.sinv), (size_t)rows * sizeof(float));
+    if (ldh_out) *ldh_out = x.ldh;
+  });
+}
+
+int dd_op_pack_mk_weights(const float* w, int nout, int nin, uint16_t* packed, float* sinv) {
+  return op_guard([&] {
+    if (!w || nout < 1 || nin < 1 || nin % 16 || nout % 32)
+      throw std::invalid_argument("dd_op_pack_mk_weights: null pointer, nin % 16 or nout % 32");
+    std::vector<_Float16> pk;
+    std::vector<float> si;
+    pack_mk_weights(w, nout, nin, pk, si);
+    if (packed) std::memcpy(packed, pk.data(), pk.size() * sizeof(_Float16));
+    if (sinv) std::memcpy(sinv, si.data(), si.size() * sizeof(float));
+  });
+}
 
 int dd_op_mk_linear(const float* A, int K, const float* wgt, const float* bias, float* out, int N, void* stream) {
   return op_guard([&] {

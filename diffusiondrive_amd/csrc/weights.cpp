@@ -107,7 +107,8 @@ size_t Arena::add_zero(size_t n) {
 
 // f16x3 weight split (conv_x3.hip header): per row r, s_r = 2^e with max|w_r| * s_r in
 // [2^14, 2^15] (exact power-of-two scaling, no fp16 overflow, lo parts clear of the subnormal
-// range); hi = f16(w * s_r), lo = f16(w * s_r - hi), both RNE; sinv[r] = 1 / s_r.
+// range); hi = f16(w * s_r), lo = f16(w * s_r - hi), both RNE; sinv[r] = 1 / s_r. e <= kSplitMaxExp
+// (weights.h) keeps s_r and 1 / s_r normal fp32 numbers on rows below 2^-112; a zero row keeps s_r = 1.
 SplitW prep_split(Arena& ar, const float* w, int rows, int K) {
   SplitW x;
   x.ldh = (K + 7) / 8 * 8;
@@ -127,6 +128,7 @@ SplitW prep_split(Arena& ar, const float* w, int rows, int K) {
       int ex;
       std::frexp(amax, &ex);  // amax = f * 2^ex, f in [0.5, 1)
       e = 15 - ex;            // amax * 2^e in [2^14, 2^15)
+      e = std::min(e, kSplitMaxExp);
     }
     const float s = std::ldexp(1.0f, e);
     sinv[r] = std::ldexp(1.0f, -e);

@@ -322,6 +322,15 @@ const char* dd_op_last_error(void);
 /* Kernel and tile configuration of the calling thread's last conv / GEMM launch (dd_op_* or forward), e.g.
  * "conv_x6<8,32,128,4,2>": lets tests prove which route a shape took. */
 const char* dd_op_last_kernel(void);
+/* The host's f16x3 / bf16 weight split (weights.cpp:prep_split) on host pointers, no device call: w fp32
+ * [rows][K] -> hi, lo (fp16 bits) and b16 (bf16 bits), each [rows][ldh] with ldh = K rounded up to 8 (padding
+ * zero), sinv[rows] = 1 / s_r, *ldh_out = ldh. Any output may be null. */
+int dd_op_split_weights(const float* w, int rows, int K, uint16_t* hi, uint16_t* lo, uint16_t* b16, float* sinv,
+                        int* ldh_out);
+/* The megakernels' weight packing (decoder_mk.hip:pack_mk_weights) on host pointers, no device call: w fp32
+ * [nout][nin], nin % 16 == 0, nout % 32 == 0 -> packed[nout * nin * 2] fp16 bits in MFMA-fragment order (block
+ * (nt, ks) of 64 lanes x (8 hi, 8 lo), lane = col % 32 + 32 ((k % 16) / 8)), sinv[nout]. */
+int dd_op_pack_mk_weights(const float* w, int nout, int nin, uint16_t* packed, float* sinv);
 /* The decoder megakernel's GEMM core (decoder_mk.hip): out[32][N] = A[32][K] W^T + bias, A and W fp32 (W
  * [N][K] packed on the host into the MFMA-fragment f16x3 image), K % 256 == 0, N % 32 == 0; synchronous. */
 int dd_op_mk_linear(const float* A, int K, const float* wgt, const float* bias, float* out, int N, void* stream);

@@ -1,5 +1,5 @@
 """The cases of the per-element f16x3 bound tests (test_f16x3_bound.py, test_f16x3_bound_gpu.py): shapes, expected
-routes and the four input families, all built from test_ops_gpu.rnd. A case's tensors, its float64 terms and its rho are
+routes and the five input families, all built from test_ops_gpu.rnd. A case's tensors, its float64 terms and its rho are
 computed once per process and shared (never modified).
 
 Families
@@ -10,6 +10,17 @@ Families
   chanscale6   input channel k's activations x 2^-c_k and its weights x 2^c_k, c_k from 0 .. 6 (channel 0 keeps 0, the
                last channel takes 6): the function is unchanged, the activation lo parts are subnormal.
   chanscale12  the same with c_k from 0 .. 12.
+  rowrange     output channel n's weights x 2^e_n over the whole of fp32: ROWRANGE cycles through tiny rows (2^-140,
+               2^-135, 2^-127, 2^-120, 2^-114, and two rows whose largest |weight| is set to 2^-113 and to
+               2^-113 (1 - 2^-24), either side of the scale 2^127 the split would need), one exactly-zero row and
+               normal rows (2^-60 .. 2^110); the last channel and the last channel of every 32-column tile are tiny
+               or zero with normal neighbours. Bias and residual are scaled with the row on the normal rows and stay
+               at unit scale on the tiny and zero rows - a folded BatchNorm's shift survives its dead gamma. (A
+               weight is the unit-scale draw times a power of two, exact while it stays a normal fp32 number; below
+               2^-126 the product rounds to a subnormal, and that stored fp32 value is the case's weight.) The bound
+               gains a flush allowance, err <= rho D + T + FLOOR with FLOOR = 2 max |float64 dot product| over the
+               case's tiny rows: a kernel that returns exactly the bias for such a row passes, NaN, Inf or a wrong
+               bias does not; rho is measured over the normal rows.
 """
 import functools
 
@@ -20,7 +31,7 @@ import torch.nn.functional as F
 import f16x3_emul as E
 from test_ops_gpu import rnd
 
-FAMILIES = ("uniform", "rowscale", "chanscale6", "chanscale12")
+FAMILIES = ("uniform", "rowscale", "chanscale6", "chanscale12", "rowrange")
 
 # (name, (B, H, W, Cin, Cout, k, stride, pad, relu, res), environment, route). The environment switches are the ones
 # test_ops_gpu uses to reach conv_x6's routed forms at a small batch (DDMI_X3_SPLIT=1: no K split ahead of conv_x6,
@@ -64,6 +75,62 @@ def row_exponents(N, seed):
     return torch.tensor(e, dtype=torch.float32)
 
 
+# the rowrange family's cycle: an exponent, or "zero" / "edge_ok" / "edge_over" (the rows whose largest |weight| is
+# 2^-113 / the fp32 number below it). Tiny (T) and normal (N) alternate: T N T N T N T N T N T N T T
+EDGE = {"edge_ok": 2.0 ** -113, "edge_over": 2.0 ** -113 * (1.0 - 2.0 ** -24)}
+ROWRANGE = (-140, 0, -135, 40, "edge_ok", -60, -127, 90, "zero", -30, -120, 110, "edge_over", -114)
+TINY_MAX = -113  # rows at or below 2^-113 are the family's tiny rows
+
+
+def _is_tiny(item):
+    return isinstance(item, str) or item <= TINY_MAX
+
+
+def row_range(N, seed):
+    """The rowrange item of every output channel: ROWRANGE cycled from an offset, then the last channel and the last
+    channel of every 32-column tile made tiny or zero and their neighbours normal."""
+    items = [ROWRANGE[(n + seed) % len(ROWRANGE)] for n in range(N)]
+    tiny = [i for i in ROWRANGE if _is_tiny(i)]
+    normal = [i for i in ROWRANGE if not _is_tiny(i)]
+    ends = sorted({N - 1} | set(range(31, N, 32)))
+    for j, n in enumerate(ends):
+        items[n] = tiny[(seed + j) % len(tiny)]
+        for m in (n - 1, n + 1):
+            if 0 <= m < N and m not in ends:
+                items[m] = normal[(seed + j + m) % len(normal)]
+    return items
+
+
+def tiny_rows(N, seed):
+    """bool (N,): the tiny and zero rows of ``row_range``."""
+    return torch.tensor([_is_tiny(i) for i in row_range(N, seed)])
+
+
+def _row_range_apply(w, b, r, seed, emax=None):
+    """``emax``: the normal rows' exponents above it are replaced by it (an op whose epilogue squares its values)."""
+    N = w.shape[0]
+    items = [i if emax is None or isinstance(i, str) else min(i, emax) for i in row_range(N, seed)]
+    rows = w.double().reshape(N, -1).clone()
+    keep = torch.ones(N, dtype=torch.float64)       # the scale of bias and residual
+    for n, item in enumerate(items):
+        if item == "zero":
+            rows[n] = 0.0
+        elif isinstance(item, str):
+            amax, k = rows[n].abs().max(0)
+            _, ex = torch.frexp(amax)               # amax 2^(-113 - ex) in [2^-114, 2^-113)
+            rows[n] *= 2.0 ** (-113 - int(ex))
+            rows[n, k] = torch.sign(rows[n, k]) * EDGE[item]
+        else:
+            rows[n] *= 2.0 ** item
+            if not _is_tiny(item):
+                keep[n] = 2.0 ** item
+    w = rows.float().view(w.shape)                  # RNE into fp32's subnormals below 2^-126
+    b = None if b is None else (b.double() * keep).float()
+    if r is not None:
+        r = (r.double() * (keep.view(1, -1, 1, 1) if r.dim() == 4 else keep)).float()
+    return w, b, r
+
+
 def chan_exponents(C, cmax, seed):
     """c_k of the chanscale families."""
     c = _ints(0, cmax, C, seed)
@@ -77,6 +144,8 @@ def _apply(family, x, w, b, r, seed):
     axis 1 (conv) or -1 (linear). Powers of two: every scaled value is exact."""
     if family == "uniform":
         return x, w, b, r
+    if family == "rowrange":
+        return (x,) + _row_range_apply(w, b, r, seed)
     if family == "rowscale":
         s = torch.exp2(row_exponents(w.shape[0], seed))
         w = w * s.view(-1, *([1] * (w.dim() - 1)))
@@ -92,14 +161,27 @@ def _apply(family, x, w, b, r, seed):
     return x / cx, w * cw, b, r
 
 
+def _tiny(family, N, seed):
+    return tiny_rows(N, seed) if family == "rowrange" else None
+
+
 class Case:
     """One op case: inputs in the oracle's layout, the float64 terms (ref before ReLU, D, T) and the measured rho."""
 
-    def __init__(self, x, w, b, r, stride, padding, relu):
+    def __init__(self, x, w, b, r, stride, padding, relu, tiny=None):
         self.x, self.w, self.b, self.r = x, w, b, r
         self.stride, self.padding, self.relu = stride, padding, relu
         self.terms = E.terms(x, w, b, r, stride, padding)
-        self.rho, self.rho_emul, self.rho_fp32 = E.measure_rho(x, w, b, r, stride, padding, t=self.terms)
+        # rowrange: ``tiny`` marks its tiny and zero rows; rho over the others, FLOOR from the tiny rows' dot products
+        self.tiny = tiny
+        self.normal = None if tiny is None else ~tiny
+        self.floor = 0.0
+        if tiny is not None:
+            xd, wd = x.double(), w.double()[tiny]
+            dot = F.conv2d(xd, wd, None, stride, padding) if w.dim() == 4 else F.linear(xd, wd)
+            self.floor = 2.0 * float(dot.abs().max())
+        self.rho, self.rho_emul, self.rho_fp32 = E.measure_rho(x, w, b, r, stride, padding, t=self.terms,
+                                                               rows=self.normal)
 
     def emul(self, **kw):
         if self.w.dim() == 4:
@@ -108,7 +190,13 @@ class Case:
 
     def ratio(self, out):
         """Largest err / bound of ``out`` (the oracle's layout)."""
-        return E.bound_ratio(out, *self.terms, self.rho, self.relu)
+        return E.bound_ratio(out, *self.terms, self.rho, self.relu, self.floor)
+
+    def normal_limit_min(self):
+        """Smallest rho D + T over the elements of the normal rows (rowrange: what FLOOR must stay far below)."""
+        _, D, T = self.terms
+        lim = (self.rho * D + T).movedim(1 if self.w.dim() == 4 else -1, 0)
+        return float(lim[self.normal].min())
 
     def truth(self):
         ref = self.terms[0]
@@ -123,7 +211,7 @@ def conv_case(shape, family):
     b = rnd(Cout, seed=213)
     Ho, Wo = E.out_hw(H, W, k, s, p)
     r = rnd(B, Cout, Ho, Wo, seed=214) if res else None
-    return Case(*_apply(family, x, w, b, r, 215), s, p, bool(relu))
+    return Case(*_apply(family, x, w, b, r, 215), s, p, bool(relu), tiny=_tiny(family, Cout, 215))
 
 
 class StemCase(Case):
@@ -132,9 +220,10 @@ class StemCase(Case):
 
     def pooled_ratio(self, out):
         ref, D, T = self.terms
-        lim = F.max_pool2d(self.rho * D + T, 3, 2, 1)
+        lim = F.max_pool2d(self.rho * D + T + self.floor, 3, 2, 1)
         err = (out.double() - F.max_pool2d(F.relu(ref), 3, 2, 1)).abs()
-        return float(torch.where(err > 0, err / lim, torch.zeros_like(err)).max())
+        ratio = torch.where(err > 0, err / lim, torch.zeros_like(err))
+        return float(torch.where(torch.isfinite(err), ratio, torch.full_like(err, float("inf"))).max())
 
     def emul_pooled(self, **kw):
         return F.max_pool2d(self.emul(**kw), 3, 2, 1)
@@ -150,7 +239,7 @@ def stem_case(B, C, H, W, family):
     w4[:, live:] = 0.0
     b = rnd(64, seed=223)
     xs, ws, b, _ = _apply(family, x[:, :live], w4[:, :live], b, None, 225)
-    case = StemCase(xs, ws, b, None, 2, 3, True)
+    case = StemCase(xs, ws, b, None, 2, 3, True, tiny=_tiny(family, 64, 225))
     case.w4 = torch.cat([ws, torch.zeros(64, 4 - live, 7, 7)], 1)
     case.x_in = torch.cat([xs, torch.zeros(B, 1, H, W)], 1) if C == 4 else xs
     return case
@@ -161,4 +250,4 @@ def mk_case(K, N, family):
     a = rnd(32, K, seed=231)
     w = rnd(N, K, seed=232, scale=1.0 / np.sqrt(K))
     b = rnd(N, seed=233)
-    return Case(*_apply(family, a, w, b, None, 235), 1, 0, False)
+    return Case(*_apply(family, a, w, b, None, 235), 1, 0, False, tiny=_tiny(family, N, 235))

@@ -2,8 +2,8 @@
 from any kernel's code - and the per-element error metric the f16x3 bound tests use (test_f16x3_bound.py on the CPU,
 test_f16x3_bound_gpu.py on the device).
 
-Arithmetic: a weight row r is scaled by s_r = 2^e with max|w_r| s_r in [2^14, 2^15) and split into hi = f16(w s_r),
-lo = f16(w s_r - hi); an activation is split unscaled, hi = f16(x), lo = f16(x - hi) (fp16 subnormals kept, as the
+Arithmetic: a weight row r is scaled by s_r = 2^e with max|w_r| s_r in [2^14, 2^15) - e <= 126, so that s_r and 1 / s_r
+are normal fp32 numbers on the rows below 2^-112 too - and split into hi = f16(w s_r), lo = f16(w s_r - hi); an activation is split unscaled, hi = f16(x), lo = f16(x - hi) (fp16 subnormals kept, as the
 hardware's conversion keeps them). A product is al wh + ah wl + ah wh, every f16 x f16 product exact in fp32, summed in
 the accumulator's type in steps of 16 along K (K order: tap, then channel); the sum is multiplied by 1 / s_r, then bias,
 residual and ReLU follow in fp32.
@@ -32,16 +32,18 @@ KSTEP = 16
 SUB_LIMIT = 2.0 ** -2   # activations below it may have a subnormal lo part
 SUB_ERR = 2.0 ** -25    # half of fp16's subnormal spacing
 RHO_MAX = 1e-6
+SPLIT_MAX_EXP = 126     # the weight scale's largest exponent: 2^126 and 2^-126 are both normal fp32 numbers
 
 
 # --------------------------------------------------------------------------- the split
 def split_weights(w):
     """(hi, lo, sinv) of a (rows, K) weight matrix: per-row power-of-two scale, two fp16 images, the inverse scale
-    (fp32). The scaling is exact in fp32; a zero row keeps scale 1."""
+    (fp32). The scaling is exact in fp32; a zero row keeps scale 1; e <= 126, so a row with max|w_r| < 2^-112 is
+    scaled by 2^126 (2^127 would leave 1 / s subnormal, 2^128 is inf) and fills less of the fp16 range."""
     w = w.float()
     amax = w.abs().amax(1)
     _, ex = torch.frexp(amax)                      # amax = f 2^ex, f in [0.5, 1)
-    e = torch.where(amax > 0, 15 - ex, torch.zeros_like(ex))
+    e = torch.where(amax > 0, (15 - ex).clamp_max(SPLIT_MAX_EXP), torch.zeros_like(ex))
     s = torch.ldexp(torch.ones_like(amax), e)
     v = w * s[:, None]
     hi = v.half()
@@ -187,10 +189,11 @@ def eta(out, x, w, bias=None, res=None, stride=1, padding=0, relu=False):
     return (out.double() - ref).abs(), D
 
 
-def measure_rho(x, w, bias=None, res=None, stride=1, padding=0, t=None):
+def measure_rho(x, w, bias=None, res=None, stride=1, padding=0, t=None, rows=None):
     """rho of one case, (rho, emulation's max (err - T)+ / D, plain fp32's max err / D): computed on the CPU from the
     emulation with fp32 accumulation and from PyTorch's fp32 op on the same inputs, before any ReLU. ``t`` may carry
-    the case's ``terms`` to spare a second float64 pass."""
+    the case's ``terms`` to spare a second float64 pass; ``rows`` (bool per output channel) restricts the maxima to
+    those channels (the rowrange family measures rho over its normal rows)."""
     ref, D, T = t if t is not None else terms(x, w, bias, res, stride, padding)
     if w.dim() == 4:
         em = conv_x3_emul(x, w, bias, res, stride, padding)
@@ -198,18 +201,23 @@ def measure_rho(x, w, bias=None, res=None, stride=1, padding=0, t=None):
     else:
         em = linear_x3_emul(x, w, bias, res)
         f32 = linear_x3_emul(x, w, bias, res, mutant="plain_fp32")
+    if rows is not None:
+        ax = 1 if w.dim() == 4 else -1
+        ref, D, T, em, f32 = (v.movedim(ax, 0)[rows] for v in (ref, D, T, em, f32))
     Dp = D.clamp_min(torch.finfo(torch.float64).tiny)
     r_em = float((((em.double() - ref).abs() - T).clamp_min(0) / Dp).max())
     r_32 = float(((f32.double() - ref).abs() / Dp).max())
     return 4.0 * max(r_em, r_32), r_em, r_32
 
 
-def bound_ratio(out, ref, D, T, rho, relu=False):
-    """Largest err / (rho D + T) over the elements of ``out`` (float64 ``ref`` before ReLU); <= 1 meets the bound."""
+def bound_ratio(out, ref, D, T, rho, relu=False, floor=0.0):
+    """Largest err / (rho D + T + floor) over the elements of ``out`` (float64 ``ref`` before ReLU); <= 1 meets the
+    bound. An element of ``out`` that is not finite is infinitely far off."""
     truth = F.relu(ref) if relu else ref
-    lim = rho * D + T
+    lim = rho * D + T + floor
     err = (out.double() - truth).abs()
     ratio = torch.where(err > 0, err / lim.clamp_min(torch.finfo(torch.float64).tiny), torch.zeros_like(err))
+    ratio = torch.where(torch.isfinite(err), ratio, torch.full_like(err, float("inf")))
     return float(ratio.max())
 
 

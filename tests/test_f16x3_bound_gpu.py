@@ -10,7 +10,9 @@ fp32 on the same inputs, never from the device; rho <= 1e-6 is a condition). The
 tests' uniform inputs, output rows scaled by 2^-20 .. 2^10 (the per-row weight scale and its index in every epilogue,
 small channels the max-norm bar of test_ops_gpu.close() cannot see) and input channels scaled down by up to 2^6 / 2^12
 with the weights compensated (subnormal activation lo parts: a kernel that flushes them or loses a lo image is 8 - 79
-times over the bound, the documented arithmetic stays under it). The CPU companion test_f16x3_bound.py shows that the
+times over the bound, the documented arithmetic stays under it), and output rows over the whole of fp32 (rowrange:
+2^-140 .. 2^110, a zero row and the rows either side of the split's threshold 2^-113, with a flush allowance FLOOR
+added to the bound; see test_weight_range.py). The CPU companion test_f16x3_bound.py shows that the
 emulation meets the bound on every case and that four mutants of it do not.
 
 Part 2: fresh handles on rescale_util's dicts (hidden channels of every BasicBlock and ReLU MLP scaled by 2^-U{0..SPREAD},
