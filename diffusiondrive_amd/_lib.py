@@ -61,6 +61,18 @@ class DDInputs(ctypes.Structure):
     ]
 
 
+class DDSimParams(ctypes.Structure):
+    """dd_sim_params: the tracker / bicycle constants of dd_simulate (include/ddmi.h)."""
+    _fields_ = [
+        ("wheel_base", ctypes.c_double), ("dt", ctypes.c_double), ("tracking_horizon", ctypes.c_int),
+        ("q_lon", ctypes.c_double), ("r_lon", ctypes.c_double), ("q_lat", ctypes.c_double * 3),
+        ("r_lat", ctypes.c_double), ("jerk_penalty", ctypes.c_double), ("curvature_rate_penalty", ctypes.c_double),
+        ("initial_curvature_penalty", ctypes.c_double), ("stopping_gain", ctypes.c_double),
+        ("stopping_velocity", ctypes.c_double), ("max_steering_angle", ctypes.c_double),
+        ("accel_time_constant", ctypes.c_double), ("steering_time_constant", ctypes.c_double),
+    ]
+
+
 MAX_SAMPLES = 32  # DD_MAX_SAMPLES
 
 # name -> (restype, argtypes)
@@ -100,6 +112,12 @@ _SIGS = {
     "dd_bev_semantic_loss": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             c_void_p, c_void_p, c_void_p]),
     "dd_bev_semantic_loss_work": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dd_default_sim_params": (None, [ctypes.POINTER(DDSimParams)]),
+    "dd_simulate_work": (ctypes.c_size_t, [ctypes.c_int]),
+    "dd_simulate_proposals": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(DDSimParams), c_void_p, c_void_p, c_void_p]),
+    "dd_simulate": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int, ctypes.c_int,
+                                   ctypes.POINTER(DDSimParams), c_void_p, c_void_p, c_void_p]),
     "dd_set_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_set_schedule": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_get_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int)]),

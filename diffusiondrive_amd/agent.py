@@ -173,6 +173,20 @@ class DiffusionDriveAgent(_Base):
         cls = _NavsimTrajectory if HAVE_NAVSIM else Trajectory
         return [cls(p) for p in poses]
 
+    def simulate_trajectories(self, predictions, ego_states: torch.Tensor, key: str = "trajectory",
+                              params=None) -> torch.Tensor:
+        """The first stage of the PDM score on the GPU (``diffusiondrive_amd.simulate``): the LQR-tracked,
+        bicycle-propagated states (..., 41, 11) float64 of every candidate in ``predictions`` - a (B, ..., 8, 3)
+        tensor, or a forward's output dict, of which ``key`` is read (``"trajectory"``, or ``"poses_reg"`` for every
+        mode) - from the scenes' start states ``ego_states`` (B, 11) float64 (pdm_simulator.py:32-79). A host tensor
+        (``forward`` returns its outputs on the CPU) is moved to the model's device."""
+        from .simulate import simulate_trajectories
+        traj = predictions[key] if isinstance(predictions, dict) else predictions
+        traj = torch.as_tensor(traj)
+        if traj.device.type != "cuda":
+            traj = traj.to(torch.device("cuda", self._transfuser_model.device))
+        return simulate_trajectories(traj, ego_states, params)
+
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).
 TransfuserAgent = DiffusionDriveAgent

@@ -17,6 +17,8 @@
                                " at " __FILE__ ":" + std::to_string(__LINE__) + ": " #expr); \
   } while (0)
 
+struct dd_sim_params;  // include/ddmi.h
+
 namespace ddmi {
 
 // Raise a kernel's dynamic-LDS limit to `bytes` once per device (the attribute is per device; the
@@ -503,5 +505,11 @@ void launch_add2(float* o, hipStream_t st);
 size_t bev_ce_partials(int B, int HW);
 void launch_bev_ce(const float* logits, const uint8_t* target, float* part, float* out, int B, int C, int HW,
                    hipStream_t st);
+
+// ---- simulate.hip: PDM proposal simulation (dd_simulate / dd_simulate_proposals). traj (float, N x 8 x 3, ego frame)
+// or proposals (double, N x 41 x 3): exactly one set; work = simulate_work_doubles(N) doubles.
+size_t simulate_work_doubles(int N);
+void launch_simulate(const float* traj, const double* proposals, const double* ego_states, int N, int per_group,
+                     const dd_sim_params& p, double* work, double* out_states, hipStream_t st);
 
 }  // namespace ddmi

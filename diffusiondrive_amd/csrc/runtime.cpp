@@ -2754,6 +2754,74 @@ int dd_destroy(dd_handle* h) {
   return guarded([&] { delete h; });
 }
 
+// ---- candidate simulation (simulate.hip): stateless, every argument checked before any device work
+void dd_default_sim_params(dd_sim_params* p) {
+  if (!p) return;
+  p->wheel_base = 3.089;
+  p->dt = 0.1;
+  p->tracking_horizon = 10;
+  p->q_lon = 10.0;
+  p->r_lon = 1.0;
+  p->q_lat[0] = 1.0;
+  p->q_lat[1] = 10.0;
+  p->q_lat[2] = 0.0;
+  p->r_lat = 1.0;
+  p->jerk_penalty = 1e-4;
+  p->curvature_rate_penalty = 1e-2;
+  p->initial_curvature_penalty = 1e-10;
+  p->stopping_gain = 0.5;
+  p->stopping_velocity = 0.2;
+  p->max_steering_angle = M_PI / 3;
+  p->accel_time_constant = 0.2;
+  p->steering_time_constant = 0.05;
+}
+
+size_t dd_simulate_work(int N) { return N > 0 ? ddmi::simulate_work_doubles(N) : 0; }
+
+static int simulate_entry(const char* who, const float* traj, const double* proposals, bool from_traj, int num_poses,
+                          const double* ego_states, int N, int per_group, const dd_sim_params* p, double* work,
+                          double* out_states, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument(std::string(who) + ": " + what); };
+    if (N <= 0) bad("N = " + std::to_string(N) + " must be positive");
+    if (per_group <= 0) bad("per_group = " + std::to_string(per_group) + " must be positive");
+    if (N % per_group) bad("N = " + std::to_string(N) + " is not a multiple of per_group = " + std::to_string(per_group));
+    if (from_traj && num_poses != 8)
+      bad("num_poses = " + std::to_string(num_poses) + " is not supported (8 poses at 0.5 s only)");
+    if (from_traj && !traj) bad("traj is null");
+    if (!from_traj && !proposals) bad("proposals is null");
+    if (!ego_states) bad("ego_states is null");
+    if (!p) bad("params is null");
+    if (!work) bad("work is null");
+    if (!out_states) bad("out_states is null");
+    auto positive = [&](const char* field, double v) {
+      if (!(v > 0.0)) bad(std::string("dd_sim_params.") + field + " = " + std::to_string(v) + " must be positive");
+    };
+    positive("dt", p->dt);
+    if (!(p->dt >= 1e-6)) bad("dd_sim_params.dt = " + std::to_string(p->dt) + " is below one microsecond");
+    positive("wheel_base", p->wheel_base);
+    positive("jerk_penalty", p->jerk_penalty);
+    positive("curvature_rate_penalty", p->curvature_rate_penalty);
+    positive("initial_curvature_penalty", p->initial_curvature_penalty);
+    if (p->tracking_horizon < 2 || p->tracking_horizon > 40)
+      bad("dd_sim_params.tracking_horizon = " + std::to_string(p->tracking_horizon) + " must be in [2, 40]");
+    ddmi::launch_simulate(from_traj ? traj : nullptr, from_traj ? nullptr : proposals, ego_states, N, per_group, *p,
+                          work, out_states, static_cast<hipStream_t>(stream));
+  });
+}
+
+int dd_simulate_proposals(const double* proposals, const double* ego_states, int N, int per_group,
+                          const dd_sim_params* params, double* work, double* out_states, void* stream) {
+  return simulate_entry("dd_simulate_proposals", nullptr, proposals, false, 8, ego_states, N, per_group, params, work,
+                        out_states, stream);
+}
+
+int dd_simulate(const float* traj, int num_poses, const double* ego_states, int N, int per_group,
+                const dd_sim_params* params, double* work, double* out_states, void* stream) {
+  return simulate_entry("dd_simulate", traj, nullptr, true, num_poses, ego_states, N, per_group, params, work,
+                        out_states, stream);
+}
+
 int dd_set_profiling(dd_handle* h, int enable) {
   return guarded([&] {
     if (!h) throw std::invalid_argument("null handle");

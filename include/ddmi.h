@@ -21,6 +21,12 @@
  *                  made from (no reference counterpart: the reference widens them to float on the CPU,
  *                  transfuser_features.py:57-138)
  *   dd_destroy  <- agent teardown (no reference counterpart; frees device memory)
+ *   dd_simulate_proposals  <- PDMSimulator.simulate_proposals      pdm_planner/simulation/pdm_simulator.py:32-79
+ *                  (BatchLQRTracker.track_trajectory, batch_lqr.py:134-464; the profile fits of
+ *                  batch_lqr_utils.py:59-249; BatchKinematicBicycleModel.propagate_state,
+ *                  batch_kinematic_bicycle.py:76-185), the first stage of the PDM score (pdm_score.py:83-140)
+ *   dd_simulate  <- transform_trajectory + get_trajectory_as_array (pdm_score.py:24-80) on the planner's 8 poses,
+ *                  then the same simulation
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
  * handle must be serialised by the caller (the reference runs one agent per worker process,
@@ -288,6 +294,61 @@ int dd_numerics_flags(dd_handle* h, unsigned* flags, int clear);
 /* Copy a named internal buffer (e.g. "p3", "keyval", "cross_bev", "reg_s0l1") of the last
  * forward into dst (device pointer), at most `count` floats; *actual = buffer length. */
 int dd_tap(dd_handle* h, const char* name, float* dst, size_t count, size_t* actual, void* stream);
+
+/* ---- candidate simulation (the first stage of NAVSIM's PDM score, on the GPU) ------------------ */
+/* The PDM score (navsim/evaluate/pdm_score.py:83-140) never scores a planner's waypoints: it interpolates them to a
+ * 41-state proposal at 0.1 s and runs PDMSimulator.simulate_proposals - an LQR tracker closed over a kinematic bicycle
+ * model for 40 steps - and computes every sub-score from the simulated states. These entries run that simulation for N
+ * candidates (dd_forward_samples draws up to 32 x 20 per scene) without a handle, in float64 throughout as the
+ * reference does, deterministically (no atomics; two calls on the same input are bit-equal). The sub-scores themselves
+ * (collision, drivable area, progress, TTC, comfort) are out of scope. */
+typedef struct dd_sim_params {
+  double wheel_base;                /* 3.089 m (nuPlan's get_pacifica_parameters) */
+  double dt;                        /* 0.1 s: the proposal's sampling interval and the tracker's discretisation; the
+                                       bicycle model steps int(dt * 1e6) us read back as time_us * 1e-6
+                                       (pdm_simulator.py:56,62), one ulp below 0.1 */
+  int tracking_horizon;             /* 10 steps (batch_lqr.py:68); 2..40 */
+  double q_lon, r_lon;              /* 10, 1 (batch_lqr.py:63-64) */
+  double q_lat[3], r_lat;           /* {1, 10, 0}, 1 (batch_lqr.py:65-66) */
+  double jerk_penalty;              /* 1e-4 (batch_lqr.py:69) */
+  double curvature_rate_penalty;    /* 1e-2 (batch_lqr.py:70) */
+  double initial_curvature_penalty; /* 1e-10 (batch_lqr_utils.py:14) */
+  double stopping_gain;             /* 0.5 (batch_lqr.py:71) */
+  double stopping_velocity;         /* 0.2 m/s (batch_lqr.py:72) */
+  double max_steering_angle;        /* pi / 3 (batch_kinematic_bicycle.py:37) */
+  double accel_time_constant;       /* 0.2 s (batch_kinematic_bicycle.py:38) */
+  double steering_time_constant;    /* 0.05 s (batch_kinematic_bicycle.py:39) */
+} dd_sim_params;
+/* Fill *p with the reference defaults listed above. */
+void dd_default_sim_params(dd_sim_params* p);
+/* Device scratch of one call over N candidates, in doubles (the velocity fit's factor, each candidate's velocity and
+ * curvature profiles, dd_simulate's proposals). The calls allocate nothing. */
+size_t dd_simulate_work(int N);
+/* The simulator proper (pdm_simulator.py:32-79). proposals: device double (N, 41, 3) [x, y, heading] at 0.1 s;
+ * ego_states: device double (G, 11) in the StateIndex order of pdm_enums.py:4-17 (x, y, heading, velocity x / y,
+ * acceleration x / y, steering angle, steering rate, angular velocity, angular acceleration), G = N / per_group:
+ * candidate n starts from ego_states[n / per_group] (per_group = 20 x S for dd_forward_samples' poses_reg); work:
+ * dd_simulate_work(N) device doubles; out_states: device double (N, 41, 11), state 0 = the start state, the heading
+ * in [-pi, pi) (nuPlan's principal_value). Per candidate: the least-squares velocity / acceleration fit with the
+ * jerk regulariser exactly as batch_lqr_utils.py:59-70 builds it (NOT a difference matrix: the second slice
+ * assignment overwrites the first), the curvature / curvature-rate fit (a 40 x 40 SPD solve per candidate, Cholesky
+ * where the reference multiplies by a pseudo-inverse), then 40 steps of tracker command (the stopping P controller
+ * where both the reference and the current velocity are <= stopping_velocity, else the one-step longitudinal LQR and
+ * the tracking_horizon-step lateral LQR) and bicycle update. DD_ERR_INVALID before any device work, with the argument
+ * or field named in dd_last_error(): N <= 0, per_group <= 0, N % per_group != 0, a null pointer, dt, wheel_base or a
+ * penalty (jerk, curvature rate, initial curvature) <= 0, tracking_horizon outside 2..40. */
+int dd_simulate_proposals(const double* proposals, const double* ego_states, int N, int per_group,
+                          const dd_sim_params* params, double* work, double* out_states, void* stream);
+/* The same from the planner's own output: traj = device float (N, num_poses, 3) in the ego frame, exactly the
+ * trajectory / poses_reg tensors the forwards write (any leading shape flattened to N), read in place. The proposal is
+ * built on the device first, restating transform_trajectory + get_trajectory_as_array (pdm_score.py:24-80) on the
+ * exact 0.1 s grid: knot 0 is the start state's rear-axle pose, knot k = 1..8 is ego o pose_k (x0 + cos(h0) x -
+ * sin(h0) y, y0 + sin(h0) x + cos(h0) y, h0 + h); x and y are linear between knots at weights j / 5; the heading is
+ * unwrapped along the knots (np.unwrap), then linear. The reference evaluates nuPlan's InterpolatedTrajectory at
+ * absolute timestamps truncated to whole microseconds, which moves a sample by <= 1 us of travel; this grid is exact.
+ * num_poses must be 8 (poses at 0.5 s: the only num_poses dd_create accepts), else DD_ERR_INVALID. */
+int dd_simulate(const float* traj, int num_poses, const double* ego_states, int N, int per_group,
+                const dd_sim_params* params, double* work, double* out_states, void* stream);
 
 /* ---- input feature builder (TransfuserFeatureBuilder.compute_features on the GPU) ---------- */
 /* Camera feature (transfuser_features.py:57-77): crop + stitch + cv2 INTER_LINEAR resize +
