@@ -178,6 +178,11 @@ _SIGS = {
                                        ctypes.c_int, ctypes.c_int, ctypes.c_int, c_void_p]),
     "dd_op_gpt_attention": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.c_int, c_void_p]),
+    "dd_op_gpt_attention_rows": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                c_void_p]),
+    "dd_op_layernorm_groups": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_longlong, ctypes.c_int, c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

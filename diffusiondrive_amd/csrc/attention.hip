@@ -60,7 +60,7 @@ constexpr int kQB = 64;  // query rows per workgroup (4 tiles of 16)
 
 template <int HS>
 __global__ __launch_bounds__(256) void gpt_attn_kernel(const float* __restrict__ qkv, float* __restrict__ y, int T,
-                                                       int C, int heads, int nqb, float scale) {
+                                                       int C, int heads, int nqb, float scale, int qfirst) {
   constexpr int KQ = HS / 4;                // k slice per lane group in phase 1
   constexpr int KC = KQ <= 32 ? KQ : 16;    // k floats per lane per register chunk
   constexpr int NCH = KQ / KC;              // chunks (1 for hs <= 128: q stays in registers)
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(256) void gpt_attn_kernel(const float* __restrict__
   const int b = bid / heads;
   const int64_t ld = 3 * (int64_t)C;
   const float* base = qkv + (int64_t)b * T * ld + (int64_t)h * HS;
-  const int q0 = qb * kQB;
+  const int q0 = qfirst + qb * kQB;  // nqb query blocks from row qfirst (the whole sequence: 0, T / kQB)
 
   // ---- phase 1: scores
   {
@@ -291,7 +291,7 @@ struct AttnLds {
 
 template <int HS, int NW, int SS>
 __global__ __launch_bounds__(64 * NW) void gpt_attn_x3_kernel(const float* __restrict__ qkv, float* __restrict__ y, int T,
-                                                              int C, int heads, float scale) {
+                                                              int C, int heads, float scale, int qfirst, int nqt) {
   static_assert(SS == 2 || SS == 3, "score operand splits");
   using LY = AttnLds<HS, SS>;
   constexpr int NB = HS >= 64 ? 1 : 2;  // LDS stages (one for the large heads: 2-3 workgroups per CU)
@@ -303,7 +303,9 @@ __global__ __launch_bounds__(64 * NW) void gpt_attn_x3_kernel(const float* __res
   constexpr int NPK = (NKE + NT - 1) / NT, NPV = (NVE + NT - 1) / NT;
   extern __shared__ __attribute__((aligned(16))) _Float16 LH[];
   float* AL = reinterpret_cast<float*>(LH + NB * LY::STAGE) + (threadIdx.x >> 6) * 32;  // per-wave 32 floats
-  const int G = T / (32 * NW);  // workgroups per (scene, head)
+  // the query window: nqt 32-query blocks from row qfirst (the whole sequence: 0, T / 32); every query walks all
+  // T / 32 key tiles in the same order whatever the window
+  const int G = nqt / NW;  // workgroups per (scene, head)
   const int bh = blockIdx.x / G, grp = blockIdx.x - bh * G;
   const int b = bh / heads, h = bh - (bh / heads) * heads;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 31, hh = lane >> 5;
@@ -312,7 +314,7 @@ __global__ __launch_bounds__(64 * NW) void gpt_attn_x3_kernel(const float* __res
   const float* Qg = base + h * HS;
   const float* Kg = base + C + h * HS;
   const float* Vg = base + 2 * C + h * HS;
-  const int q0 = (grp * NW + wave) * 32;
+  const int q0 = qfirst + (grp * NW + wave) * 32;
 
   // Q^T B fragments: k = head dimension, n = query q0 + li (SS = 2: only .h / .m are used)
   Split3 qf[NKS];
@@ -521,17 +523,25 @@ __global__ __launch_bounds__(64 * NW) void gpt_attn_x3_kernel(const float* __res
 
 }  // namespace
 
-void launch_gpt_attention(const float* qkv, int B, int T, int C, int heads, float* y, int prec, hipStream_t st) {
+void launch_gpt_attention(const float* qkv, int B, int T, int C, int heads, float* y, int prec, hipStream_t st,
+                          int q_first, int q_count, int nw_force) {
   if (heads <= 0 || C % heads) throw std::runtime_error("gpt_attention: C % heads != 0");
   const int hs = C / heads;
+  if (q_count < 0) q_count = T - q_first;
+  const int qgran = prec != 0 ? 32 : kQB;
+  if (q_first < 0 || q_count <= 0 || q_first + q_count > T || q_first % qgran || q_count % qgran)
+    throw std::runtime_error("gpt_attention: the query window must be whole blocks of " + std::to_string(qgran) +
+                             " rows inside [0, T)");
   if (prec != 0) {
     // f16x3 form: T % 32 == 0, NW (waves per workgroup) = the largest divisor of T / 32 that is <= DDMI_ATTN_NW
     // (DDMI_ATTN_NW128 at hs = 128; compile-time constants, profiles/round3_i_attn_ss.txt)
     if (T % 32 || T > 1024 || (reinterpret_cast<uintptr_t>(qkv) & 15) || C % 4)
       throw std::runtime_error("gpt_attention(f16x3): T % 32 == 0, T <= 1024, 16-B aligned qkv, C % 4 == 0");
-    const int nq = T / 32;
-    // the largest instantiated wave count (10, 5, 4, 3, 2, 1) <= the cap that divides T / 32
+    const int nq = q_count / 32;
+    // the largest instantiated wave count (10, 5, 4, 3, 2, 1) <= the cap that divides the window's 32-query blocks
+    // (nw_force: that count instead, for the micro-benchmarks)
     int nw = hs >= 128 ? DDMI_ATTN_NW128 : DDMI_ATTN_NW;
+    if (nw_force > 0) nw = nw_force;
     while (nw > 1 && (nq % nw || (nw > 5 && nw != 10))) --nw;
     const float scale = (float)(1.0 / std::sqrt((double)hs));
     const dim3 grid((unsigned)((int64_t)B * heads * (nq / nw))), block((unsigned)(64 * nw));
@@ -544,12 +554,12 @@ void launch_gpt_attention(const float* qkv, int B, int T, int C, int heads, floa
       auto go2 = [&](auto SSC) {
         constexpr int SS = decltype(SSC)::value;
         switch (nw) {
-          case 10: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 10, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale); break;
-          case 5: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 5, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale); break;
-          case 4: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 4, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale); break;
-          case 3: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 3, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale); break;
-          case 2: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 2, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale); break;
-          case 1: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 1, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale); break;
+          case 10: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 10, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale, q_first, nq); break;
+          case 5: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 5, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale, q_first, nq); break;
+          case 4: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 4, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale, q_first, nq); break;
+          case 3: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 3, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale, q_first, nq); break;
+          case 2: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 2, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale, q_first, nq); break;
+          case 1: hipLaunchKernelGGL((gpt_attn_x3_kernel<HS, 1, SS>), grid, block, lds, st, qkv, y, T, C, heads, scale, q_first, nq); break;
           default: throw std::runtime_error("gpt_attention(f16x3): no kernel for " + std::to_string(nw) + " waves");
         }
       };
@@ -571,14 +581,14 @@ void launch_gpt_attention(const float* qkv, int B, int T, int C, int heads, floa
     throw std::runtime_error("gpt_attention: T must be a multiple of 64 with T/4 % 8 == 0, and <= 512");
   if ((reinterpret_cast<uintptr_t>(qkv) & 15) || (C % 4))
     throw std::runtime_error("gpt_attention: qkv must be 16-byte aligned with C % 4 == 0");
-  const int nqb = T / kQB;
+  const int nqb = q_count / kQB;
   const size_t lds = (size_t)kQB * T * sizeof(float);
   const float scale = (float)(1.0 / std::sqrt((double)hs));  // math.sqrt in the reference
   const dim3 grid((unsigned)((int64_t)B * heads * nqb)), block(256);
   switch (hs) {
 #define AT(HS)                                                                                          \
   case HS:                                                                                              \
-    hipLaunchKernelGGL((gpt_attn_kernel<HS>), grid, block, lds, st, qkv, y, T, C, heads, nqb, scale); \
+    hipLaunchKernelGGL((gpt_attn_kernel<HS>), grid, block, lds, st, qkv, y, T, C, heads, nqb, scale, q_first); \
     break;
     AT(16) AT(32) AT(64) AT(128) AT(256) AT(512)
 #undef AT

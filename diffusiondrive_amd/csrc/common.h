@@ -111,6 +111,10 @@ struct ConvArgs {
   float* ln_out = nullptr;
   const float* ln_g = nullptr;
   const float* ln_b = nullptr;
+  // Rows the dispatcher chooses the tile form for (0: this launch's own M). A launch over a subset of the rows of
+  // another GEMM of the same Linear shapes names that GEMM's M here, so both run the same kernel instance: the
+  // subset's rows get the K walk and epilogue of the full launch by construction, whatever the batch.
+  int64_t route_rows = 0;
 };
 constexpr unsigned DD_NUM_F16_OVERFLOW = 1u;  // an activation |x| >= 65504 met the f16x3 split
 constexpr unsigned DD_NUM_SYNC_TIMEOUT = 2u;  // a megakernel's inter-workgroup wait gave up (tfdec_mk groups)
@@ -376,15 +380,22 @@ void launch_bilinear(View4 in, int B, int Hi, int Wi, int C, View4 out, int Ho, 
 // Row LayerNorm (eps 1e-5): y[r] = LN(x[r] + res[r / res_div]) * g + b, then optional FiLM
 // y = y * (1 + film_scale) + film_shift - one FiLM vector for every row, or (film_div > 0) the FiLM vectors of row
 // group r / film_div at film_ld floats apart. C <= 2048. In-place allowed (y == x).
+// group_rows > 0: the rows come in groups of group_rows, row r at (r / group_rows) * group_stride +
+// (r % group_rows) * ld of x and of y (rows = groups * group_rows; no residual); a row's arithmetic is unchanged.
 void launch_layernorm(const float* x, int64_t ldx, const float* res, int64_t ldres, int res_div,
                       const float* g, const float* b, const float* film_scale, const float* film_shift,
                       float* y, int64_t ldy, int rows, int C, hipStream_t st, int film_div = 0,
-                      int64_t film_ld = 0);
+                      int64_t film_ld = 0, int group_rows = 0, int64_t group_stride = 0);
 // Fused GPT self-attention (attention.hip): y[b,t,h*hs..] = softmax(q.k^T / sqrt(hs)) v per
 // (scene, head) from the packed projection qkv [B][T][3C]; y is [B][T][C]. T % 64 == 0, (T/4) % 8 == 0,
 // T <= 512, hs in {16, ..., 512}.
 // prec 0: fp32 MFMA; 1: f16x3 MFMA (three-way split scores), the f16x3 / bf16 modes
-void launch_gpt_attention(const float* qkv, int B, int T, int C, int heads, float* y, int prec, hipStream_t st);
+// q_first / q_count: only the query rows [q_first, q_first + q_count) of every scene are computed and written (whole
+// blocks of 32 rows for prec 1 / 2, of 64 for prec 0; q_count < 0: to the end), against all T keys in the same tile
+// order, so a row's result does not depend on the window. nw_force > 0 (micro-benchmarks): the f16x3 form's waves per
+// workgroup.
+void launch_gpt_attention(const float* qkv, int B, int T, int C, int heads, float* y, int prec, hipStream_t st,
+                          int q_first = 0, int q_count = -1, int nw_force = 0);
 // Fused GPT block tail at C = 64 / 128 (gpt_tail.hip): x += proj(y); h = ln2(x); x += mlp(h); hb = lnn(x) in one
 // launch over M token rows, f16x3 products bit-identical to the unfused conv_x3 / conv_x5 chain.
 struct GptTailW {

@@ -296,9 +296,10 @@ void launch_conv_gemm(const ConvArgs& a, hipStream_t st) {
     throw std::runtime_error("conv_gemm: operand extent >= 2 GiB (split the batch)");
   if ((int64_t)a.Ho * a.out_sh >= (int64_t(1) << 31) || (int64_t)a.Ho * a.res_sh >= (int64_t(1) << 31))
     throw std::runtime_error("conv_gemm: per-image output extent too large");
-  const int64_t tiles_big = ((M + 127) / 128) * (int64_t)((a.Cout + 127) / 128) * a.batch;
+  const int64_t Mr = a.route_rows > 0 ? a.route_rows : M;  // the rows the form is chosen for
+  const int64_t tiles_big = ((Mr + 127) / 128) * (int64_t)((a.Cout + 127) / 128) * a.batch;
   if (a.Cout <= 64) {
-    if (((M + 127) / 128) * (int64_t)a.batch >= 512)
+    if (((Mr + 127) / 128) * (int64_t)a.batch >= 512)
       launch_cfg<2, 1>(a, M, K, st);
     else
       launch_cfg<1, 1>(a, M, K, st);

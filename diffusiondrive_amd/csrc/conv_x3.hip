@@ -686,10 +686,11 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t st) {
   }
   g_last_conv = "conv_x3";
   if (launch_x3_split(a0, M, K, st)) return;
-  const int64_t t128 = ((M + 127) / 128) * (int64_t)((a0.Cout + 127) / 128);
+  const int64_t Mr = a0.route_rows > 0 ? a0.route_rows : M;  // the rows the form is chosen for
+  const int64_t t128 = ((Mr + 127) / 128) * (int64_t)((a0.Cout + 127) / 128);
   const bool generic = !(a0.Cin % BK == 0 && a0.KH * a0.KW <= 32);
   if (a0.Cout <= 64) {
-    if (!generic && (M + 255) / 256 >= 256)
+    if (!generic && (Mr + 255) / 256 >= 256)
       launch_x3_cfg<4, 1, 2, 2>(a0, M, K, st);  // 256 x 64
     else
       launch_x3_cfg<2, 2, 1, 1>(a0, M, K, st);  // 64 x 64

@@ -463,7 +463,8 @@ static void launch_x5_cfg(const ConvArgs& a, int M, int K, hipStream_t st) {
 // slower than conv_x3 on the GPT shapes (tools/micro/gemm_x3_bench.py) and are not routed here.
 bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st) {
   if (a.prec != 0 && a.prec != 1) return false;
-  const int64_t m256 = (M + 255) / 256;
+  const int64_t Mr = a.route_rows > 0 ? a.route_rows : M;  // the rows the form is chosen for (M: the rows launched)
+  const int64_t m256 = (Mr + 255) / 256;
   const int64_t n256 = (a.Cout + 255) / 256, n128 = (a.Cout + 127) / 128;
   // 1x1 stride-1 GEMMs (the GPT M = 20480 token GEMMs): 256 x 256 tiles already pay at half a chip of
   // tiles when Cout is a multiple of 256 from 512 up (MLP-down K = 2048: 172 -> 161 us, qkv C = 256:
@@ -482,11 +483,11 @@ bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st) {
   // bf16 (config C4's trunk mode): the short-K 1x1 GEMMs - the ResNet-50 bottleneck expands, HBM-bound on their
   // outputs - on the same two-per-CU tiles (C4 forward -0.35 ms; the compute-heavy GEMMs and the strided downsamples
   // lost there, tools/gpu_r6aa.sh, profiles/round6/x5_t128_ab.md)
-  if (M >= 16384 && a.prec == 1 && gemm && K <= 256 && a.Cin % KC == 0 && a.Cout % 128 == 0) {
+  if (Mr >= 16384 && a.prec == 1 && gemm && K <= 256 && a.Cin % KC == 0 && a.Cout % 128 == 0) {
     launch_x5_cfg<4, 2, 1, 2, 2>(a, M, K, st);
     return true;
   }
-  if (M >= 16384 && a.prec == 0 && a.Cin % KC == 0 && a.Cout % 128 == 0) {
+  if (Mr >= 16384 && a.prec == 0 && a.Cin % KC == 0 && a.Cout % 128 == 0) {
     const bool mlp = gemm && ((a.Cout >= 1024 && a.Cout % 1024 == 0 && K <= 512) || (K >= 1024 && a.Cout >= 256) ||
                               (a.Cout == K && K >= 512));
     const bool s2 = a.stride == 2 && a.KH == 3 && a.KW == 3 &&
@@ -497,7 +498,7 @@ bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st) {
       return true;
     }
   }
-  if (gemm && K <= 512 && (a.Cout == 512 || a.Cout == 1024) && M >= 16384) {
+  if (gemm && K <= 512 && (a.Cout == 512 || a.Cout == 1024) && Mr >= 16384) {
     launch_x5_cfg<2, 4, 3, 2, 2>(a, M, K, st);  // 192 x 256, 8 waves
     return true;
   }

@@ -337,16 +337,20 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
                                                         const float* __restrict__ g, const float* __restrict__ b,
                                                         const float* __restrict__ fs, const float* __restrict__ fb,
                                                         int film_div, int64_t film_ld,
-                                                        float* y, int64_t ldy, int rows, int C) {
+                                                        float* y, int64_t ldy, int rows, int C, int grows,
+                                                        int64_t gstride) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
+  // grouped rows (grows > 0): row r of x and y sits in group r / grows, gstride floats apart
+  const int64_t goff = grows > 0 ? (int64_t)(row / grows) * gstride : 0;
+  const int rg = grows > 0 ? row % grows : row;
   if (fs && film_div > 0) {  // per-group FiLM rows (training head: one time embedding per scene)
     fs += (int64_t)(row / film_div) * film_ld;
     fb += (int64_t)(row / film_div) * film_ld;
   }
   float v[32];
-  const float* xr = x + (int64_t)row * ldx;
+  const float* xr = x + goff + (int64_t)rg * ldx;
   const float* rr = res ? res + (int64_t)(row / res_div) * ldres : nullptr;
   float s = 0.f;
 #pragma unroll
@@ -369,7 +373,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
     q += d * d;
   }
   const float rstd = rsqrtf(wave_sum(q) / (float)C + 1e-5f);
-  float* yr = y + (int64_t)row * ldy;
+  float* yr = y + goff + (int64_t)rg * ldy;
 #pragma unroll
   for (int i = 0; i < 32; ++i) {
     const int c = lane + 64 * i;
@@ -390,7 +394,8 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
                                                            const float* __restrict__ g, const float* __restrict__ b,
                                                            const float* __restrict__ fs, const float* __restrict__ fb,
                                                            int film_div, int64_t film_ld,
-                                                           float* y, int64_t ldy, int rows) {
+                                                           float* y, int64_t ldy, int rows, int grows,
+                                                           int64_t gstride) {
   constexpr int C = LPR * 4 * VPL;
   const int sub = threadIdx.x % LPR;
   const int row = (blockIdx.x * 256 + threadIdx.x) / LPR;
@@ -400,7 +405,10 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
     fs += (int64_t)(r / film_div) * film_ld;
     fb += (int64_t)(r / film_div) * film_ld;
   }
-  const float4* xr = reinterpret_cast<const float4*>(x + (int64_t)r * ldx);
+  // grouped rows (grows > 0): row r of x and y sits in group r / grows, gstride floats apart
+  const int64_t goff = grows > 0 ? (int64_t)(r / grows) * gstride : 0;
+  const int rg = grows > 0 ? r % grows : r;
+  const float4* xr = reinterpret_cast<const float4*>(x + goff + (int64_t)rg * ldx);
   const float4* rr = res ? reinterpret_cast<const float4*>(res + (int64_t)(r / res_div) * ldres) : nullptr;
   float4 v[VPL];
   float s = 0.f;
@@ -430,7 +438,7 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
   for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
   const float rstd = rsqrtf(q / (float)C + 1e-5f);
   if (!live) return;
-  float4* yr = reinterpret_cast<float4*>(y + (int64_t)row * ldy);
+  float4* yr = reinterpret_cast<float4*>(y + goff + (int64_t)rg * ldy);
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c4 = sub + LPR * i;
@@ -458,11 +466,15 @@ __global__ __launch_bounds__(256) void layernorm_v4_kernel(const float* __restri
 
 void launch_layernorm(const float* x, int64_t ldx, const float* res, int64_t ldres, int res_div, const float* g,
                       const float* b, const float* film_scale, const float* film_shift, float* y, int64_t ldy,
-                      int rows, int C, hipStream_t st, int film_div, int64_t film_ld) {
+                      int rows, int C, hipStream_t st, int film_div, int64_t film_ld, int group_rows,
+                      int64_t group_stride) {
   if (C > 2048) throw std::runtime_error("layernorm: C > 2048");
   if (rows == 0) return;
+  if (group_rows < 0 || (group_rows > 0 && (rows % group_rows || res)))
+    throw std::runtime_error("layernorm: grouped rows need rows % group_rows == 0 and no residual");
   auto al = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = C >= 64 && (C & (C - 1)) == 0 && ldx % 4 == 0 && ldy % 4 == 0 && (!res || ldres % 4 == 0) &&
+                   group_stride % 4 == 0 &&
                    al(x) && al(y) && al(res) && al(g) && al(b) && al(film_scale) && al(film_shift);
   if (vec) {
     const int lpr = C / 4 < 64 ? C / 4 : 64;
@@ -470,7 +482,7 @@ void launch_layernorm(const float* x, int64_t ldx, const float* res, int64_t ldr
     const int rd = res_div < 1 ? 1 : res_div;
 #define LNV(L, V)                                                                                                  \
   hipLaunchKernelGGL((layernorm_v4_kernel<L, V>), grid, dim3(256), 0, st, x, ldx, res, ldres, rd, g, b, film_scale, \
-                     film_shift, film_div, film_ld, y, ldy, rows)
+                     film_shift, film_div, film_ld, y, ldy, rows, group_rows, group_stride)
     switch (C) {
       case 64: LNV(16, 1); break;
       case 128: LNV(32, 1); break;
@@ -484,7 +496,8 @@ void launch_layernorm(const float* x, int64_t ldx, const float* res, int64_t ldr
     return;
   }
   hipLaunchKernelGGL(layernorm_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, x, ldx, res, ldres,
-                     res_div < 1 ? 1 : res_div, g, b, film_scale, film_shift, film_div, film_ld, y, ldy, rows, C);
+                     res_div < 1 ? 1 : res_div, g, b, film_scale, film_shift, film_div, film_ld, y, ldy, rows, C, group_rows,
+                     group_stride);
   DD_HIP_CHECK(hipGetLastError());
 }
 

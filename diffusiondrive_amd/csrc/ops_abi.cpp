@@ -455,4 +455,22 @@ int dd_op_gpt_attention(const float* qkv, float* y, int B, int T, int C, int hea
   return op_guard([&] { launch_gpt_attention(qkv, B, T, C, heads, y, prec, S(stream)); });
 }
 
+int dd_op_gpt_attention_rows(const float* qkv, float* y, int B, int T, int C, int heads, int prec, int q_first,
+                             int q_count, int waves, void* stream) {
+  return op_guard([&] {
+    if (q_count < 1) throw std::invalid_argument("dd_op_gpt_attention_rows: q_count < 1");
+    launch_gpt_attention(qkv, B, T, C, heads, y, prec, S(stream), q_first, q_count, waves);
+  });
+}
+
+int dd_op_layernorm_groups(const float* x, const float* g, const float* b, float* y, int groups, int group_rows,
+                           long long group_stride, int C, void* stream) {
+  return op_guard([&] {
+    if (groups < 1 || group_rows < 1 || group_stride < (long long)group_rows * C)
+      throw std::invalid_argument("dd_op_layernorm_groups: groups, group_rows >= 1 and non-overlapping groups");
+    launch_layernorm(x, C, nullptr, 0, 1, g, b, nullptr, nullptr, y, C, groups * group_rows, C, S(stream), 0, 0,
+                     group_rows, group_stride);
+  });
+}
+
 }  // extern "C"

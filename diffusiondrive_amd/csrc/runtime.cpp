@@ -203,6 +203,9 @@ class Model {
   bool vproj_union = true;
   bool ln_fold = true;  // DDMI_LN_FOLD=0: every GPT LayerNorm as its own launch (gemm_ln)
   int gpt_tail_env = -1;  // DDMI_GPT_TAIL=0 / 1: force the C <= 128 GPT block tail off / on (default: B <= 16)
+  // the last block of the last scale's GPT computes only the LiDAR-token rows after its K / V (fuse());
+  // DDMI_GPT_LAST_ROWS=0: all 320 rows
+  bool gpt_last_rows = true;
   int vproj_umax = 1 << 30;  // DDMI_VPROJ_UMAX (tests): tiles with a larger union take the gathered fallback
   int vproj_usplit_env = 0;  // DDMI_VPROJ_USPLIT (1, 2, 4, 8): the union form's K split, else chosen from B
   bool stem_nchw = true;             // see use_nchw_stem
@@ -343,6 +346,7 @@ class Model {
     if (const char* e = getenv("DDMI_VPROJ_UNION")) vproj_union = atoi(e) != 0;
     if (const char* e = getenv("DDMI_LN_FOLD")) ln_fold = atoi(e) != 0;
     if (const char* e = getenv("DDMI_GPT_TAIL")) gpt_tail_env = atoi(e) != 0;
+    if (const char* e = getenv("DDMI_GPT_LAST_ROWS")) gpt_last_rows = atoi(e) != 0;
     if (const char* e = getenv("DDMI_VPROJ_UMAX")) vproj_umax = std::max(0, atoi(e));
     if (const char* e = getenv("DDMI_VPROJ_USPLIT")) {
       vproj_usplit_env = atoi(e);
@@ -1282,9 +1286,12 @@ class Model {
             const float* res = nullptr, int64_t ldr = 0) {
     gemm_g(L, A, (int64_t)M * lda, lda, 1, M, C, (int64_t)M * ldc, ldc, relu, res, (int64_t)M * ldr, ldr);
   }
+  // route_rows: see ConvArgs::route_rows (a row subset of another GEMM takes that GEMM's tile form)
   void gemm_g(const Lin& L, const float* A, int64_t a_gs, int64_t a_rs, int G, int R, float* C, int64_t c_gs,
-              int64_t c_rs, bool relu = false, const float* res = nullptr, int64_t r_gs = 0, int64_t r_rs = 0) {
+              int64_t c_rs, bool relu = false, const float* res = nullptr, int64_t r_gs = 0, int64_t r_rs = 0,
+              int64_t route_rows = 0) {
     ConvArgs a;
+    a.route_rows = route_rows;
     a.in = A;
     a.in_sn = a_gs;
     a.in_sh = a_rs;
@@ -1397,6 +1404,12 @@ class Model {
           int64_t film_ld = 0) {
     launch("layernorm", 0, [&] {
       launch_layernorm(x, ldx, res, ldres, res_div, W(p.g), W(p.b), fs, fb, y, ldy, rows, p.c, st, film_div, film_ld);
+    });
+  }
+  // G groups of R rows, the groups gs floats apart in x and y (one launch)
+  void ln_g(const LNp& p, const float* x, float* y, int64_t ld, int G, int R, int64_t gs) {
+    launch("layernorm", 0, [&] {
+      launch_layernorm(x, ld, nullptr, 0, 1, W(p.g), W(p.b), nullptr, nullptr, y, ld, G * R, p.c, st, 0, 0, R, gs);
     });
   }
 
@@ -1515,15 +1528,39 @@ class Model {
     // Hb = ln1(x) before each block's qkv, ln2(x) before its MLP, ln_f(x) at the end. Where the GEMM producing x
     // (proj, MLP-down) spans the row in one tile (C <= 128), its epilogue writes the LayerNorm too (gemm_ln)
     bool hb_ready = false;  // Hb already holds ln1 of the next block (or ln_f after the last)
+    // After the last scale only the LiDAR tokens go on (i2l below; the image upsample-add is skipped), and token rows
+    // meet only in self-attention, where the image tokens are keys and values. So the last block of that GPT needs
+    // its image rows in ln1 and the K / V of qkv only: the attention queries, proj, ln2, the MLP and ln_f run over the
+    // 64 LiDAR rows of every scene (B row groups T C apart), each row's arithmetic as in the full launches: the GEMMs
+    // run the kernel instance the dispatcher picks for the block's full M = B T rows (route_rows), so a row's K walk
+    // is the full-row block's at every batch. The image rows of X / Hb / Y / MLP keep what the earlier launches left.
+    const bool last_rows = gpt_last_rows && i + 1 == 4;
     for (size_t bi = 0; bi < g.blocks.size(); ++bi) {
       const GptBlockW& w = g.blocks[bi];
       if (!hb_ready) ln(w.ln1, X, C, Hb, C, M);
+      const bool live = last_rows && bi + 1 == g.blocks.size();
+      // (the Q third of this GEMM is dead for the image rows too; K | V over all rows + Q over the LiDAR rows as two
+      // launches took 126 -> 85 + 20 us, which the bench did not show: profiles/gpt_last_rows.md)
       gemm(w.qkv, Hb, C, M, QKV, 3 * C);
       // softmax(Q K^T / sqrt(hs)) V per (scene, head), one fused launch (attention.hip): fp32 MFMA in the
       // fp32 mode, f16x3 MFMA in the f16x3 mode (two-way split scores) and the bf16 mode (three-way)
       const int aprec = (gemm_mode == DD_GEMM_FP32 || !gpt_attn_x3 || C / 4 > 128 || T % 32 || T > 1024)
                             ? 0
                             : (gemm_mode == DD_GEMM_BF16 ? 2 : 1);
+      if (live) {
+        const int nl = T - nimg;
+        const int64_t gs = (int64_t)T * C, off = (int64_t)nimg * C;
+        launch("attn", 4.0 * B * nl * T * (double)C,
+               [&] { launch_gpt_attention(QKV, B, T, C, 4, Y, aprec, st, nimg, nl); });
+        gemm_g(w.proj, Y + off, gs, C, B, nl, X + off, gs, C, false, X + off, gs, C, M);  // x = x + proj(y)
+        ln_g(w.ln2, X + off, Hb + off, C, B, nl, gs);
+        float* ML = MLP + (int64_t)nimg * 4 * C;
+        gemm_g(w.mlp0, Hb + off, gs, C, B, nl, ML, 4 * gs, 4 * C, true, nullptr, 0, 0, M);
+        gemm_g(w.mlp2, ML, 4 * gs, 4 * C, B, nl, X + off, gs, C, false, X + off, gs, C, M);  // x = x + mlp(ln2 x)
+        ln_g(g.lnf, X + off, Hb + off, C, B, nl, gs);
+        hb_ready = true;
+        continue;
+      }
       launch("attn", 4.0 * B * T * T * (double)C, [&] { launch_gpt_attention(QKV, B, T, C, 4, Y, aprec, st); });
       const LNp& nx = bi + 1 < g.blocks.size() ? g.blocks[bi + 1].ln1 : g.lnf;
       // C <= 128 in f16x3 at small batches: proj + ln2 + MLP + the next LayerNorm as one launch (gpt_tail.hip,

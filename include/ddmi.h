@@ -454,6 +454,16 @@ int dd_op_mha_small(const float* q, const float* k, const float* v, float* out, 
  * scores on two-way fp16 splits, three products), prec 2: the same with three-way score splits and six products
  * (the bf16 mode's choice); both T % 32 == 0, T <= 1024, C/heads in {16, 32, 64, 128}. */
 int dd_op_gpt_attention(const float* qkv, float* y, int B, int T, int C, int heads, int prec, void* stream);
+/* The same over a query window: only rows [q_first, q_first + q_count) of every scene of y are computed and written
+ * (whole blocks of 32 rows for prec 1 / 2, of 64 for prec 0), against all T keys in the full launch's tile order, so
+ * those rows equal the full launch's bit for bit. waves > 0: the f16x3 form's waves per workgroup (micro-benchmarks;
+ * 0 = the library's choice). */
+int dd_op_gpt_attention_rows(const float* qkv, float* y, int B, int T, int C, int heads, int prec, int q_first,
+                             int q_count, int waves, void* stream);
+/* dd_op_layernorm (no residual, no FiLM) over `groups` groups of `group_rows` rows of C floats, the groups
+ * group_stride floats apart in x and in y; rows between the groups are neither read nor written. */
+int dd_op_layernorm_groups(const float* x, const float* g, const float* b, float* y, int groups, int group_rows,
+                           long long group_stride, int C, void* stream);
 
 #ifdef __cplusplus
 }
