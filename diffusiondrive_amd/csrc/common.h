@@ -95,7 +95,7 @@ struct ConvArgs {
   // stays the per-image one the consumer indexes.
   const int* rowcount = nullptr;
   int rowcap = 0;
-  // Fused GPT token pooling (conv_x6 only; launch_conv_gemm reports it through last_conv_pooled()):
+  // Fused GPT token pooling (conv_x6 only; launch_conv_gemm reports it in ConvRoute::pooled):
   // when pool_out is set, the mean of every pool_p x pool_p output window (after bias / residual / ReLU)
   // plus pool_add[wy * pool_add_sh + wx * pool_add_sw + c] (if set) is also written to
   // pool_out[n * pool_sn + wy * pool_sh + wx * pool_sw + c] - the avgpool_kernel arithmetic, same order.
@@ -105,9 +105,9 @@ struct ConvArgs {
   const float* pool_add = nullptr;
   int64_t pool_add_sh = 0, pool_add_sw = 0;
   // Fused LayerNorm of the finished output rows (conv_x3's quad epilogue with one N tile spanning the row, Cout 64
-  // or 128; launch_conv_gemm reports it through last_conv_ln()): ln_out (the same row layout as out) receives
+  // or 128; launch_conv_gemm reports it in ConvRoute::ln): ln_out (the same row layout as out) receives
   // LayerNorm(out row) * ln_g + ln_b with layernorm_v4's arithmetic and lane order (bit-identical to the separate
-  // launch). Not fused: ln_out untouched, last_conv_ln() false.
+  // launch). Not fused: ln_out untouched, ConvRoute::ln false.
   float* ln_out = nullptr;
   const float* ln_g = nullptr;
   const float* ln_b = nullptr;
@@ -298,32 +298,32 @@ __device__ inline bool epi_quads(const ConvArgs& a, const Acc (&acc)[TM][TN], ch
   return bad;
 }
 #endif
-void launch_conv_gemm(const ConvArgs& a, hipStream_t st);
-void launch_conv_x3(const ConvArgs& a, hipStream_t st);
+// What a conv / GEMM dispatch did, returned by the launchers below.
+struct ConvRoute {
+  // "conv_gemm", "conv_x3", "conv_x5", "conv_x6", "stem_pool" (the runtime's profiler attributes launch time per
+  // kernel with it); nullptr: launch_stem_pool refused the shape and launched nothing
+  const char* kernel = nullptr;
+  // kernel + tile configuration, e.g. "conv_x6<8,32,128,4,2>" (TH, TW, BN, wave grid), "conv_x5<256,256>",
+  // "conv_x3<128,128,f16x3>"; "" when nothing was launched
+  const char* config = "";
+  bool pooled = false;  // the launch also wrote ConvArgs::pool_out
+  bool ln = false;      // the launch also wrote ConvArgs::ln_out
+};
+ConvRoute launch_conv_gemm(const ConvArgs& a, hipStream_t st);
+ConvRoute launch_conv_x3(const ConvArgs& a, hipStream_t st);
 // Fused stem conv 7x7/2 (Cin 4, Cout 64, f16x3) + bias + ReLU + maxpool 3x3/2 into pool_out (B,Hp,Wp,64)
-// (stem_pool.hip); false when `a` is not such a stem (then nothing is launched).
+// (stem_pool.hip); kernel == nullptr when `a` is not such a stem (then nothing is launched).
 // src (optional): the device word holding the address of the reference's NCHW input of src_c channels (read by the
 // kernel; the NHWC4 a.in is then unused). u8 = 0: that input is fp32; 1: the uint8 (B, H, W, 3) HWC image (src_c 3);
 // 2: the planar uint8 (B, src_c, H, W) tensor - byte k then stands for the fp32 value lut[k] (256 floats, device).
-bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st,
-                      const void* const* src = nullptr, int src_c = 0, int u8 = 0, const float* lut = nullptr);
+ConvRoute launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st,
+                           const void* const* src = nullptr, int src_c = 0, int u8 = 0, const float* lut = nullptr);
 // Device-side input table: tab[0] = a, tab[1] = b (one thread; launched per forward outside the captured graph).
 // The entries are untyped addresses: fp32 or uint8 features, as the stem form that reads them expects.
 void launch_set_ptrs(const void** tab, const void* a, const void* b, hipStream_t st);
 // The LiDAR byte table: lut[c] = (float)((double)min(c, hist_max) / (double)hist_max), c = 0..255 (the expression of
 // the feature builder's finalize pass, features.hip).
 void launch_lidar_lut(float* lut, int hist_max, hipStream_t st);
-// name of the kernel the last conv / GEMM dispatch on this thread went to ("conv_gemm", "conv_x3",
-// "conv_x5", "conv_x6"); the runtime's profiler attributes launch time per kernel with it
-const char* last_conv_kernel();
-bool last_conv_pooled();           // did the last launch_conv_gemm also write ConvArgs::pool_out?
-void set_last_conv_pooled(bool p);
-bool last_conv_ln();               // did the last launch_conv_gemm also write ConvArgs::ln_out?
-void set_last_conv_ln(bool p);
-// the kernel + tile configuration of the calling thread's last conv / GEMM launch, e.g.
-// "conv_x6<8,32,128,4,2>" (TH, TW, BN, wave grid), "conv_x5<256,256>", "conv_x3<128,128,f16x3>"
-const char* last_conv_config();
-void set_last_conv_config(const char* cfg);
 
 // ----------------------------------------------------------------------------------------
 // The gathered value_proj (value_proj.hip): value rows = ReLU(conv3x3(map) + bias) at the scenes' distinct tap

@@ -263,18 +263,11 @@ static void launch_cfg(const ConvArgs& a, int M, int K, hipStream_t st) {
   DD_HIP_CHECK(hipGetLastError());
 }
 
-void set_last_conv_kernel(const char* k);  // conv_x3.hip
-
-void launch_conv_gemm(const ConvArgs& a, hipStream_t st) {
-  set_last_conv_pooled(false);
-  set_last_conv_ln(false);
+ConvRoute launch_conv_gemm(const ConvArgs& a, hipStream_t st) {
   if (a.rowmap && !a.wh) throw std::runtime_error("conv_gemm: gathered rows need the f16x3 kernel (conv_x3)");
-  if (a.wh) {
-    launch_conv_x3(a, st);
-    return;
-  }
-  set_last_conv_kernel("conv_gemm");
-  set_last_conv_config("conv_gemm");
+  if (a.wh) return launch_conv_x3(a, st);
+  ConvRoute r;
+  r.kernel = r.config = "conv_gemm";
   if (a.Cin % 4 != 0) throw std::runtime_error("conv_gemm: Cin must be a multiple of 4");
   if ((a.in_sw % 4) || (a.in_sh % 4) || (a.in_sn % 4) || (reinterpret_cast<uintptr_t>(a.in) % 16))
     throw std::runtime_error("conv_gemm: input strides / base must be 16-byte aligned");
@@ -287,7 +280,7 @@ void launch_conv_gemm(const ConvArgs& a, hipStream_t st) {
   if (M64 >= (int64_t(1) << 31)) throw std::runtime_error("conv_gemm: M too large");
   const int M = (int)M64;
   const int K = a.KH * a.KW * a.Cin;
-  if (M == 0 || a.Cout == 0) return;
+  if (M == 0 || a.Cout == 0) return r;
   // 32-bit buffer offsets: the furthest element a launch touches must stay below 2^31 bytes.
   const int64_t in_extent = (int64_t)(a.Nimg - 1) * a.in_sn + (int64_t)(a.H - 1) * a.in_sh +
                             (int64_t)(a.W - 1) * a.in_sw + a.Cin;
@@ -308,6 +301,7 @@ void launch_conv_gemm(const ConvArgs& a, hipStream_t st) {
   } else {
     launch_cfg<1, 1>(a, M, K, st);
   }
+  return r;
 }
 
 }  // namespace ddmi

@@ -499,7 +499,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_x3_kernel(ConvArgs a, int M
 }
 
 template <int WM, int WN, int TM, int TN, int GATHER = 0>
-static void launch_x3_cfg(const ConvArgs& a, int M, int K, hipStream_t st) {
+static void launch_x3_cfg(const ConvArgs& a, int M, int K, hipStream_t st, ConvRoute& r) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int ntm = (M + BM - 1) / BM;
   const int ntn = (a.Cout + BN - 1) / BN;
@@ -508,7 +508,7 @@ static void launch_x3_cfg(const ConvArgs& a, int M, int K, hipStream_t st) {
   static const std::string name[2] = {
       "conv_x3<" + std::to_string(BM) + "," + std::to_string(BN) + ",f16x3>",
       "conv_x3<" + std::to_string(BM) + "," + std::to_string(BN) + ",bf16>"};
-  set_last_conv_config(name[a.prec == 1].c_str());
+  r.config = name[a.prec == 1].c_str();
   if constexpr (GATHER) {
     hipLaunchKernelGGL((conv_x3_kernel<WM, WN, TM, TN, 1, 0, 1>), grid, dim3(64 * WM * WN), 0, st, a, M, K, ntm, ntn);
     DD_HIP_CHECK(hipGetLastError());
@@ -578,7 +578,8 @@ static int x3_split_mode() {
   const char* se = getenv("DDMI_X3_SPLIT");
   return se ? atoi(se) : 2;
 }
-static bool launch_x3_split(const ConvArgs& a, int M, int K, hipStream_t st, int wg_target = 128) {
+static bool launch_x3_split(const ConvArgs& a, int M, int K, hipStream_t st, ConvRoute& r,
+                            int wg_target = 128) {
   if (!x3_split_mode()) return false;
   if (!a.split_part || a.prec != 0 || a.rowmap || a.Cin % BK || a.KH * a.KW > 32 || a.Cout % 4) return false;
   const int64_t tiles = (int64_t)((M + 63) / 64) * ((a.Cout + 63) / 64);
@@ -589,7 +590,7 @@ static bool launch_x3_split(const ConvArgs& a, int M, int K, hipStream_t st, int
   if (S < 2 || (int64_t)S * M * a.Cout > a.split_cap) return false;
   const int ntm = (M + 63) / 64, ntn = (a.Cout + 63) / 64;
   static const std::string name = "conv_x3<64,64,f16x3,ksplit>";
-  set_last_conv_config(name.c_str());
+  r.config = name.c_str();
   hipLaunchKernelGGL((conv_x3_kernel<2, 2, 1, 1, 1, 0, 0, 1>), dim3(ntm * ntn, S), dim3(256), 0, st, a, M, K, ntm,
                      ntn);
   DD_HIP_CHECK(hipGetLastError());
@@ -605,23 +606,13 @@ static bool launch_x3_split(const ConvArgs& a, int M, int K, hipStream_t st, int
   return true;
 }
 
-bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st);  // conv_x5.hip
-bool launch_conv_x6(const ConvArgs& a, hipStream_t st);                 // conv_x6.hip
+// both fill r.config (conv_x6 also r.pooled) when they launch
+bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st, ConvRoute& r);  // conv_x5.hip
+bool launch_conv_x6(const ConvArgs& a, hipStream_t st, ConvRoute& r);                 // conv_x6.hip
 
-static thread_local const char* g_last_conv = "conv_gemm";
-const char* last_conv_kernel() { return g_last_conv; }
-void set_last_conv_kernel(const char* k) { g_last_conv = k; }
-static thread_local bool g_last_pooled = false;
-bool last_conv_pooled() { return g_last_pooled; }
-void set_last_conv_pooled(bool p) { g_last_pooled = p; }
-static thread_local bool g_last_ln = false;
-bool last_conv_ln() { return g_last_ln; }
-void set_last_conv_ln(bool p) { g_last_ln = p; }
-static thread_local const char* g_last_cfg = "";
-const char* last_conv_config() { return g_last_cfg; }
-void set_last_conv_config(const char* c) { g_last_cfg = c; }
-
-void launch_conv_x3(const ConvArgs& a, hipStream_t st) {
+ConvRoute launch_conv_x3(const ConvArgs& a, hipStream_t st) {
+  ConvRoute r;
+  r.kernel = "conv_x3";
   if (a.Cin % 4 != 0) throw std::runtime_error("conv_x3: Cin must be a multiple of 4");
   if ((a.in_sw % 4) || (a.in_sh % 4) || (a.in_sn % 4) || (reinterpret_cast<uintptr_t>(a.in) % 16))
     throw std::runtime_error("conv_x3: input strides / base must be 16-byte aligned");
@@ -634,7 +625,7 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t st) {
   const int M = (int)M64;
   const int K = a.KH * a.KW * a.Cin;
   if (a.ldh < K) throw std::runtime_error("conv_x3: ldh < K");
-  if (M == 0 || a.Cout == 0) return;
+  if (M == 0 || a.Cout == 0) return r;
   if (a.rowmap && (a.stride != 1 || a.Cin % BK != 0 || a.KH * a.KW > 32 || a.Nimg != 1 || a.Wo != 1 ||
                    a.rowmap_nimg < 1 || a.prec != 0))
     throw std::runtime_error("conv_x3: gathered rows need a stride-1 f16x3 MODE-1 conv into Nimg=1, Wo=1");
@@ -648,19 +639,17 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t st) {
     throw std::runtime_error("conv_x3: operand extent >= 2 GiB (split the batch)");
   if ((int64_t)a.Ho * a.out_sh >= (int64_t(1) << 31) || (int64_t)a.Ho * a.res_sh >= (int64_t(1) << 31))
     throw std::runtime_error("conv_x3: per-image output extent too large");
-  set_last_conv_ln(false);
   // a fused LayerNorm of the output rows (ConvArgs::ln_out) needs one N tile spanning the row in the quad epilogue:
   // 64 x 64 tiles at Cout 64, 64 x 128 at Cout 128 (the same K order per output as every other tile: the GEMM output
   // is unchanged); otherwise the request is ignored and the caller runs its LayerNorm launch
   if (a.ln_out && a.ln_g && a.ln_b && !a.rowmap && a.KH == 1 && a.KW == 1 && (a.Cout == 64 || a.Cout == 128) &&
       epi_quads_ok(a)) {
-    g_last_conv = "conv_x3";
-    set_last_conv_ln(true);
+    r.ln = true;
     if (a.Cout == 64)
-      launch_x3_cfg<2, 2, 1, 1>(a, M, K, st);  // 64 x 64
+      launch_x3_cfg<2, 2, 1, 1>(a, M, K, st, r);  // 64 x 64
     else
-      launch_x3_cfg<2, 2, 1, 2>(a, M, K, st);  // 64 x 128
-    return;
+      launch_x3_cfg<2, 2, 1, 2>(a, M, K, st, r);  // 64 x 128
+    return r;
   }
   ConvArgs b = a;
   b.ln_out = nullptr;  // every other route ignores it
@@ -668,37 +657,33 @@ void launch_conv_x3(const ConvArgs& a, hipStream_t st) {
   // default f16x3 path: 3x3 stride-1 convs on the halo-reuse direct kernel (conv_x6.hip), other
   // grids that fill the chip on the LDS-DMA implicit GEMM (conv_x5.hip), the rest here
   if (a0.rowmap) {
-    g_last_conv = "conv_x3";
-    launch_x3_cfg<2, 2, 2, 2, 1>(a0, M, K, st);  // gathered rows: 128 x 128
-    return;
+    launch_x3_cfg<2, 2, 2, 2, 1>(a0, M, K, st, r);  // gathered rows: 128 x 128
+    return r;
   }
-  if (x3_split_mode() == 2 && launch_x3_split(a0, M, K, st, 256)) {
-    g_last_conv = "conv_x3";
-    return;
+  if (x3_split_mode() == 2 && launch_x3_split(a0, M, K, st, r, 256)) return r;
+  if (launch_conv_x6(a0, st, r)) {
+    r.kernel = "conv_x6";
+    return r;
   }
-  if (launch_conv_x6(a0, st)) {
-    g_last_conv = "conv_x6";
-    return;
+  if (launch_conv_x5(a0, M, K, st, r)) {
+    r.kernel = "conv_x5";
+    return r;
   }
-  if (launch_conv_x5(a0, M, K, st)) {
-    g_last_conv = "conv_x5";
-    return;
-  }
-  g_last_conv = "conv_x3";
-  if (launch_x3_split(a0, M, K, st)) return;
+  if (launch_x3_split(a0, M, K, st, r)) return r;
   const int64_t Mr = a0.route_rows > 0 ? a0.route_rows : M;  // the rows the form is chosen for
   const int64_t t128 = ((Mr + 127) / 128) * (int64_t)((a0.Cout + 127) / 128);
   const bool generic = !(a0.Cin % BK == 0 && a0.KH * a0.KW <= 32);
   if (a0.Cout <= 64) {
     if (!generic && (Mr + 255) / 256 >= 256)
-      launch_x3_cfg<4, 1, 2, 2>(a0, M, K, st);  // 256 x 64
+      launch_x3_cfg<4, 1, 2, 2>(a0, M, K, st, r);  // 256 x 64
     else
-      launch_x3_cfg<2, 2, 1, 1>(a0, M, K, st);  // 64 x 64
+      launch_x3_cfg<2, 2, 1, 1>(a0, M, K, st, r);  // 64 x 64
   } else if (t128 >= 512) {
-    launch_x3_cfg<2, 2, 2, 2>(a0, M, K, st);    // 128 x 128
+    launch_x3_cfg<2, 2, 2, 2>(a0, M, K, st, r);  // 128 x 128
   } else {
-    launch_x3_cfg<2, 2, 1, 1>(a0, M, K, st);    // 64 x 64
+    launch_x3_cfg<2, 2, 1, 1>(a0, M, K, st, r);  // 64 x 64
   }
+  return r;
 }
 
 }  // namespace ddmi

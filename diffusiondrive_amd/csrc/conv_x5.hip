@@ -431,14 +431,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 && TM * TN == 2) ? 4 : 
 }
 
 template <int WM, int WN, int TM, int TN, int NS, int PREC, int KCT>
-static void launch_x5_one(const ConvArgs& a, int M, int K, hipStream_t st) {
+static void launch_x5_one(const ConvArgs& a, int M, int K, hipStream_t st, ConvRoute& r) {
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   const int ntm = (M + BM - 1) / BM;
   const int ntn = (a.Cout + BN - 1) / BN;
   dim3 grid(ntm * ntn, 1, 1);
   static const std::string name = "conv_x5<" + std::to_string(BM) + "," + std::to_string(BN) +
                                   (KCT == 16 ? ",k16" : "") + (PREC ? ",bf16>" : ">");
-  set_last_conv_config(name.c_str());
+  r.config = name.c_str();
   if (a.Cin % KCT == 0 && a.KH * a.KW <= 32)
     hipLaunchKernelGGL((conv_x5_kernel<WM, WN, TM, TN, 1, NS, PREC, KCT>), grid, dim3(64 * WM * WN), 0, st, a, M, K,
                        ntm, ntn);
@@ -450,18 +450,18 @@ static void launch_x5_one(const ConvArgs& a, int M, int K, hipStream_t st) {
 // NS: stages of the 32-deep ring. (A 16-deep ring with twice the stages, bit-identical, measured slower on every GPT
 // shape: 123.6 -> 130.7 us per 256 x 256 launch; removed in round 6, git history.)
 template <int WM, int WN, int TM, int TN, int NS>
-static void launch_x5_cfg(const ConvArgs& a, int M, int K, hipStream_t st) {
+static void launch_x5_cfg(const ConvArgs& a, int M, int K, hipStream_t st, ConvRoute& r) {
   if (a.prec == 1)
-    launch_x5_one<WM, WN, TM, TN, NS + 1, 1, KC>(a, M, K, st);  // the freed B image buys a stage
+    launch_x5_one<WM, WN, TM, TN, NS + 1, 1, KC>(a, M, K, st, r);  // the freed B image buys a stage
   else
-    launch_x5_one<WM, WN, TM, TN, NS, 0, KC>(a, M, K, st);
+    launch_x5_one<WM, WN, TM, TN, NS, 0, KC>(a, M, K, st, r);
 }
 
-// Returns false when the shape is better served by conv_x3 (grids too small to fill the chip).
+// Returns false when the shape is better served by conv_x3 (grids too small to fill the chip); else fills r.config.
 // Tiles: 256 x 256 with 2 stages (128 KB), 256 x 128 / 256 x 64 with 3 (144 / 96 KB). The Cout > 128
 // grids that fill the chip only at 256 x 128, and 128 x 128 tiles for the mid-size GEMMs, measured
 // slower than conv_x3 on the GPT shapes (tools/micro/gemm_x3_bench.py) and are not routed here.
-bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st) {
+bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st, ConvRoute& r) {
   if (a.prec != 0 && a.prec != 1) return false;
   const int64_t Mr = a.route_rows > 0 ? a.route_rows : M;  // the rows the form is chosen for (M: the rows launched)
   const int64_t m256 = (Mr + 255) / 256;
@@ -484,7 +484,7 @@ bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st) {
   // outputs - on the same two-per-CU tiles (C4 forward -0.35 ms; the compute-heavy GEMMs and the strided downsamples
   // lost there, tools/gpu_r6aa.sh, profiles/round6/x5_t128_ab.md)
   if (Mr >= 16384 && a.prec == 1 && gemm && K <= 256 && a.Cin % KC == 0 && a.Cout % 128 == 0) {
-    launch_x5_cfg<4, 2, 1, 2, 2>(a, M, K, st);
+    launch_x5_cfg<4, 2, 1, 2, 2>(a, M, K, st, r);
     return true;
   }
   if (Mr >= 16384 && a.prec == 0 && a.Cin % KC == 0 && a.Cout % 128 == 0) {
@@ -494,26 +494,26 @@ bool launch_conv_x5(const ConvArgs& a, int M, int K, hipStream_t st) {
                     !(a.Cout >= 256 && (m256 * n256) % 256 == 0);
     const bool ds = a.stride == 2 && a.KH == 1 && a.KW == 1;  // the residual downsamples: -6 to -24 %
     if (mlp || s2 || ds) {
-      launch_x5_cfg<4, 2, 1, 2, 2>(a, M, K, st);
+      launch_x5_cfg<4, 2, 1, 2, 2>(a, M, K, st, r);
       return true;
     }
   }
   if (gemm && K <= 512 && (a.Cout == 512 || a.Cout == 1024) && Mr >= 16384) {
-    launch_x5_cfg<2, 4, 3, 2, 2>(a, M, K, st);  // 192 x 256, 8 waves
+    launch_x5_cfg<2, 4, 3, 2, 2>(a, M, K, st, r);  // 192 x 256, 8 waves
     return true;
   }
   if (a.Cout <= 64) {
     if (m256 < 256) return false;
-    launch_x5_cfg<4, 1, 2, 2, 3>(a, M, K, st);  // 256 x 64, 4 waves
+    launch_x5_cfg<4, 1, 2, 2, 3>(a, M, K, st, r);  // 256 x 64, 4 waves
   } else if (a.Cout > 128 && m256 * n256 >= 256) {
     // (4 waves of 128 x 128 at one wave per SIMD, 512 VGPRs: 2.8x slower on the C = 512 qkv / MLP-up shapes, round 6)
-    launch_x5_cfg<4, 2, 2, 4, 2>(a, M, K, st);  // 256 x 256, 8 waves
+    launch_x5_cfg<4, 2, 2, 4, 2>(a, M, K, st, r);  // 256 x 256, 8 waves
   } else if (a.Cout <= 128 && m256 * n128 >= 256) {
-    launch_x5_cfg<4, 2, 2, 2, 3>(a, M, K, st);  // 256 x 128, 8 waves
+    launch_x5_cfg<4, 2, 2, 2, 3>(a, M, K, st, r);  // 256 x 128, 8 waves
   } else if (gemm && a.Cout >= 512 && a.Cout % 256 == 0 && m256 * n256 >= 128) {
-    launch_x5_cfg<4, 2, 2, 4, 2>(a, M, K, st);
+    launch_x5_cfg<4, 2, 2, 4, 2>(a, M, K, st, r);
   } else if (gemm && a.Cout % 256 == 128 && m256 * n128 >= 192) {
-    launch_x5_cfg<4, 2, 2, 2, 3>(a, M, K, st);
+    launch_x5_cfg<4, 2, 2, 2, 3>(a, M, K, st, r);
   } else {
     return false;
   }

@@ -570,7 +570,7 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
 }
 
 template <int TH, int TW, int BN, int WM, int WN, int D, int NSLOT, int SH, int PREC>
-static void launch_x6_one(const ConvArgs& a_in, hipStream_t st) {
+static void launch_x6_one(const ConvArgs& a_in, hipStream_t st, ConvRoute& r) {
   ConvArgs a = a_in;
   // fused token pooling: whole tiles only, windows inside tiles, 16-B aligned channel quads
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
@@ -579,34 +579,34 @@ static void launch_x6_one(const ConvArgs& a_in, hipStream_t st) {
                     a.pool_sw % 4 == 0 && (!a.pool_add || (al16(a.pool_add) && a.pool_add_sh % 4 == 0 &&
                                                            a.pool_add_sw % 4 == 0));
   if (!pool) a.pool_out = nullptr;
-  set_last_conv_pooled(pool);
+  r.pooled = pool;
   const int tiles_x = (a.Wo + TW - 1) / TW, tiles_y = (a.Ho + TH - 1) / TH;
   const int n_sp = a.Nimg * tiles_x * tiles_y;
   const int ntn = (a.Cout + BN - 1) / BN;
   static const std::string name = "conv_x6<" + std::to_string(TH) + "," + std::to_string(TW) + "," +
                                   std::to_string(BN) + "," + std::to_string(WM) + "," + std::to_string(WN) +
                                   (PREC ? ",bf16>" : ">");
-  set_last_conv_config(name.c_str());
+  r.config = name.c_str();
   hipLaunchKernelGGL((conv_x6_kernel<TH, TW, BN, WM, WN, D, NSLOT, SH, PREC>), dim3(n_sp * ntn), dim3(64 * WM * WN), 0,
                      st, a, tiles_x, tiles_y, n_sp, ntn, a.Cin / (PREC ? 64 : 32));
   DD_HIP_CHECK(hipGetLastError());
 }
 template <int TH, int TW, int BN, int WM, int WN, int D, int NSLOT, int SH>
-static void launch_x6_cfg(const ConvArgs& a, hipStream_t st) {
+static void launch_x6_cfg(const ConvArgs& a, hipStream_t st, ConvRoute& r) {
   if constexpr (SH == 0) {
     if (a.prec == 1) {
-      launch_x6_one<TH, TW, BN, WM, WN, D, NSLOT, SH, 1>(a, st);
+      launch_x6_one<TH, TW, BN, WM, WN, D, NSLOT, SH, 1>(a, st, r);
       return;
     }
   } else {
     if (a.prec == 1) throw std::runtime_error("conv_x6: bf16 takes the 8-wave configurations");
   }
-  launch_x6_one<TH, TW, BN, WM, WN, D, NSLOT, SH, 0>(a, st);
+  launch_x6_one<TH, TW, BN, WM, WN, D, NSLOT, SH, 0>(a, st, r);
 }
 
 // Returns false when the conv is not a 3x3 / stride 1 / pad 1 f16x3 / bf16 conv this kernel covers (the
-// caller then takes conv_x5 / conv_x3).
-bool launch_conv_x6(const ConvArgs& a, hipStream_t st) {
+// caller then takes conv_x5 / conv_x3); else fills r.config and r.pooled.
+bool launch_conv_x6(const ConvArgs& a, hipStream_t st, ConvRoute& r) {
   if ((a.prec != 0 && a.prec != 1) || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 ||
       a.Cin % (a.prec ? 64 : 32) != 0 || a.batch != 1 || a.b_kn)
     return false;
@@ -625,7 +625,7 @@ bool launch_conv_x6(const ConvArgs& a, hipStream_t st) {
   // the CUs idle, measured 72 us against 61: the 10 x 10 halo per 64 pixels costs more than the idle CUs.)
   if (a.Ho == 8 && a.Wo == 8 && a.Cout % 128 == 0) {
     if ((int64_t)a.Nimg * (a.Cout / 128) < 128) return false;
-    launch_x6_cfg<8, 8, 128, 2, 4, 3, 4, 0>(a, st);
+    launch_x6_cfg<8, 8, 128, 2, 4, 3, 4, 0>(a, st, r);
     return true;
   }
   const bool wide = a.Ho < 16;  // 8 x 32 tiles for the 8-row maps (layer4 of the image trunk)
@@ -641,7 +641,7 @@ bool launch_conv_x6(const ConvArgs& a, hipStream_t st) {
   // three-per-CU BN = 64 layer-1 form, 0.3 % slower at 3 lanes in flight)
   const bool sh4 = a.prec == 0 && a.Cin <= 64;
   const bool b128 = bn128;
-#define X6(TH, TW, BN, WM, WN, D, NS, SH) launch_x6_cfg<TH, TW, BN, WM, WN, D, NS, SH>(a, st)
+#define X6(TH, TW, BN, WM, WN, D, NS, SH) launch_x6_cfg<TH, TW, BN, WM, WN, D, NS, SH>(a, st, r)
   // small grids (batches of a few scenes): the routed form would run fewer than 128 workgroups, each through the
   // whole K loop; 8 x 8 pixel tiles x 64 channels (4 waves of 32 x 32) give 4-8x the workgroups at a quarter of the
   // work per K step. The K order (32-channel chunk, tap, k16 half) is every form's: bit-identical results.

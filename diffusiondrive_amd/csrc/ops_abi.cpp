@@ -12,6 +12,12 @@
 
 namespace {
 thread_local std::string g_op_err;
+// dd_op_last_kernel: the configuration of the calling thread's last conv / GEMM launch (a dispatch that launched
+// nothing leaves it)
+thread_local const char* g_op_kernel = "";
+void ran(const ddmi::ConvRoute& r) {
+  if (*r.config) g_op_kernel = r.config;
+}
 
 template <class F>
 int op_guard(F&& f) {
@@ -35,7 +41,7 @@ extern "C" {
 
 const char* dd_op_last_error(void) { return g_op_err.c_str(); }
 
-const char* dd_op_last_kernel(void) { return last_conv_config(); }
+const char* dd_op_last_kernel(void) { return g_op_kernel; }
 
 int dd_op_split_weights(const float* w, int rows, int K, uint16_t* hi, uint16_t* lo, uint16_t* b16, float* sinv,
                         int* ldh_out) {
@@ -151,7 +157,7 @@ int dd_op_conv2d(const float* in, int B, int H, int W, int Cin, const float* wgt
     a.stride = stride;
     a.pad = pad;
     a.relu = relu;
-    launch_conv_gemm(a, S(stream));
+    ran(launch_conv_gemm(a, S(stream)));
   });
 }
 
@@ -210,7 +216,7 @@ int dd_op_conv2d_x3(const float* in, int B, int H, int W, int Cin, const float* 
       a.split_part = part;
       a.split_cap = 8 * mo;
     }
-    launch_conv_gemm(a, S(stream));
+    ran(launch_conv_gemm(a, S(stream)));
     const hipError_t e = hipStreamSynchronize(S(stream));  // the split images die with `ar`
     if (part) DD_HIP_CHECK(hipFree(part));
     DD_HIP_CHECK(e);
@@ -292,7 +298,9 @@ static int dd_op_stem_pool_impl(const void* in, int src_c, int B, int H, int W, 
     }
     bool ok = false;
     try {
-      ok = launch_stem_pool(a, out, hp, wp, S(stream), src_c ? word : nullptr, src_c, u8, lut);
+      const ConvRoute r = launch_stem_pool(a, out, hp, wp, S(stream), src_c ? word : nullptr, src_c, u8, lut);
+      ran(r);
+      ok = r.kernel != nullptr;
       DD_HIP_CHECK(hipStreamSynchronize(S(stream)));  // the split images die with `ar`
     } catch (...) {
       if (word) (void)hipFree(word);
@@ -356,7 +364,7 @@ int dd_op_gemm(const float* A, int M, int K, const float* W, const float* bias, 
     a.Nimg = M;
     a.Cout = N;
     a.relu = relu;
-    launch_conv_gemm(a, S(stream));
+    ran(launch_conv_gemm(a, S(stream)));
   });
 }
 
@@ -379,7 +387,7 @@ int dd_op_gemm_batched(const float* A, const float* Bm, float* C, int batch, int
     a.in_z1 = (int64_t)M * K;
     a.w_z1 = (int64_t)K * N;
     a.out_z1 = (int64_t)M * N;
-    launch_conv_gemm(a, S(stream));
+    ran(launch_conv_gemm(a, S(stream)));
   });
 }
 

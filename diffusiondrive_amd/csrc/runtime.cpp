@@ -21,6 +21,7 @@
 #include <memory>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <vector>
 
 #ifdef DDMI_SEGV_TRACE
@@ -211,20 +212,98 @@ class Model {
   bool stem_nchw = true;             // see use_nchw_stem
   const void** in_tab = nullptr;     // device input table: [0] camera, [1] LiDAR of the current forward (untyped
                                      // addresses: fp32 or uint8 features, see InKinds)
-  // uint8 features (dd_forward_in and its siblings): the element type of the current call's camera / LiDAR input,
-  // set for the duration of one call. A uint8 camera is the (B, cam_h, cam_w, 3) HWC image, byte k = k / 255; a
-  // uint8 LiDAR the planar (B, C, lidar_h, lidar_w) clipped counts, byte c = min(c, hist_max) / hist_max. The stems
-  // (or the transposing passes) widen the bytes through the two 256-entry fp32 tables of in_lut: [0, 256) the
-  // camera's, written once at create; [256, 512) the LiDAR's, rewritten on the stream ahead of the forward when
-  // hist_max changes (lut_hist_max = the value it holds).
+  // uint8 features (dd_forward_in and its siblings): the element type of a call's camera / LiDAR input. A uint8
+  // camera is the (B, cam_h, cam_w, 3) HWC image, byte k = k / 255; a uint8 LiDAR the planar (B, C, lidar_h, lidar_w)
+  // clipped counts, byte c = min(c, hist_max) / hist_max. The stems (or the transposing passes) widen the bytes
+  // through the two 256-entry fp32 tables of in_lut: [0, 256) the camera's, written once at create; [256, 512) the
+  // LiDAR's, rewritten on the stream ahead of the forward when hist_max changes (lut_hist_max = the value it holds).
   struct InKinds {
     bool cam_u8 = false, lid_u8 = false;
     int hist_max = 0;
-  } kinds;
+  };
   float* in_lut = nullptr;
   int lut_hist_max = 0;
-  size_t cam_esz() const { return kinds.cam_u8 ? 1 : sizeof(float); }
-  size_t lid_esz() const { return kinds.lid_u8 ? 1 : sizeof(float); }
+
+  struct Outs {
+    float* traj = nullptr;
+    float* modes = nullptr;
+    float* cls = nullptr;
+    float* sem = nullptr;
+    float* ag_states = nullptr;
+    float* ag_labels = nullptr;
+    // training call: every layer's poses_reg / poses_cls and LossComputer partials ([B][2] per layer)
+    float* reg_l[2] = {nullptr, nullptr};
+    float* cls_l[2] = {nullptr, nullptr};
+    float* part_l[2] = {nullptr, nullptr};
+    // samples call: the scene's best candidate over its S x Q
+    float* best_traj = nullptr;
+    int* best_idx = nullptr;
+  };
+
+  // One forward call (or one chunk of it): everything that distinguishes it from another call on the same handle.
+  // It is passed down the forward path as an argument; the handle keeps no per-call state.
+  struct Call {
+    const void* camera = nullptr;  // fp32 NCHW or uint8, as `kinds` says
+    const void* lidar = nullptr;
+    InKinds kinds;
+    const float* status = nullptr;
+    const float* noise = nullptr;  // nullptr: drawn on the device
+    int B = 0, steps = 0;
+    // S > 1 (dd_forward_samples): every scene runs S decoder scenes (one per start noise) over its one perception
+    // pass: decoder scene d = b * S + s reads the cross-BEV map, agent K / V and ego row of scene d / S; everything
+    // else in the trajectory head is per decoder scene.
+    int samples = 1;
+    // dd_forward_train (the training-mode trajectory head as a loss evaluator, TrajectoryHead.forward_train
+    // transfuser_model_v2.py:520-576): the head runs ONE pass of the two layers from per-scene noised anchors
+    // (timesteps staged in "in_tsteps"), with per-scene time embeddings / FiLM, and - given targets ("in_target") -
+    // LossComputer's per-scene partials per layer (train_loss.hip).
+    bool train = false;
+    const int* timesteps = nullptr;  // device int32, one per scene
+    const float* target = nullptr;   // device target trajectories, or nullptr
+    float cls_w = 0.0f, reg_w = 0.0f;
+    float* loss = nullptr;  // [3] trajectory_loss_0, _1, sum of the whole call (needs target)
+    Outs o;
+
+    bool heads() const { return o.sem || o.ag_states || o.ag_labels; }
+    // also pick each scene's best candidate over its samples x Q (best_trajectory / best_index)
+    bool want_best() const { return o.best_traj || o.best_idx; }
+    size_t cam_esz() const { return kinds.cam_u8 ? 1 : sizeof(float); }
+    size_t lid_esz() const { return kinds.lid_u8 ? 1 : sizeof(float); }
+
+    // The call narrowed to scenes [b0, b0 + n): the one place that knows each input's and output's per-scene stride.
+    Call chunk(const dd_config& cfg, int b0, int n) const {
+      const size_t S = (size_t)samples, Q = (size_t)cfg.num_modes, P = (size_t)cfg.num_poses;
+      auto at = [b0](auto* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
+      Call c = *this;
+      c.B = n;
+      c.camera = at(static_cast<const char*>(camera), (size_t)3 * cfg.cam_h * cfg.cam_w * cam_esz());
+      c.lidar = at(static_cast<const char*>(lidar), (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w * lid_esz());
+      c.status = at(status, 8);
+      c.noise = at(noise, S * Q * P * 2);
+      c.timesteps = at(timesteps, 1);
+      c.target = at(target, P * 3);
+      c.o.traj = at(o.traj, S * P * 3);
+      c.o.modes = at(o.modes, S * Q * P * 3);
+      c.o.cls = at(o.cls, S * Q);
+      c.o.best_traj = at(o.best_traj, P * 3);
+      c.o.best_idx = at(o.best_idx, 1);
+      c.o.sem = at(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
+      c.o.ag_states = at(o.ag_states, (size_t)30 * 5);
+      c.o.ag_labels = at(o.ag_labels, 30);
+      for (int l = 0; l < 2; ++l) {
+        c.o.reg_l[l] = at(o.reg_l[l], Q * P * 3);
+        c.o.cls_l[l] = at(o.cls_l[l], Q);
+        c.o.part_l[l] = at(o.part_l[l], 2);
+      }
+      return c;
+    }
+    // the call's part of the program-cache key (forward_chunk adds the handle's gemm_mode and schedule)
+    std::string key() const {
+      return std::to_string(B) + "/" + std::to_string(steps) + "/" + std::to_string(heads()) +
+             (train ? (target ? "/train1" : "/train0") : "") + "/x" + std::to_string(samples) +
+             (want_best() ? "/best" : "") + "/i" + (kinds.cam_u8 ? "b" : "f") + (kinds.lid_u8 ? "b" : "f");
+    }
+  };
   const char* force_class = nullptr;  // profiling class of the next launch (else the chosen kernel)
   // bev_proj (DDMI_BEVPROJ): 2 "fused" = one bevproj.hip pass (f16x3 / bf16 modes; fp32 mode uses 1),
   // 1 "lowres" = keyval half at 8 x 8, upsample, K = 64 GEMM, LayerNorm; 0 "concat" = concat at 64 x 64
@@ -291,22 +370,11 @@ class Model {
   // rng_seed; draw block k of the stream since dd_set_seed takes draws [k Q P 2, (k + 1) Q P 2): one block per scene
   // of a forward, one per (scene, sample) of a samples forward). rng_next = the next block
   uint64_t rng_seed = 0, rng_next = 0;
-  // dd_forward_train (the training-mode trajectory head as a loss evaluator, TrajectoryHead.forward_train
-  // transfuser_model_v2.py:520-576): set for the duration of one such call. The head then runs ONE pass of the two
-  // layers from per-scene noised anchors (timesteps staged in "in_tsteps"), with per-scene time embeddings / FiLM,
-  // and - given targets ("in_target") - LossComputer's per-scene partials per layer (train_loss.hip).
-  bool train = false;
-  const int* train_t = nullptr;        // caller's timesteps of the current chunk (device int32)
-  const float* train_target = nullptr;  // caller's target trajectories of the current chunk (device, or nullptr)
-  float* ac_dev = nullptr;              // alphas_cumprod on the device (per-scene add_noise coefficients)
+  // training calls (Call::train): handle-lifetime device buffers
+  float* ac_dev = nullptr;             // alphas_cumprod on the device (per-scene add_noise coefficients)
   float* train_part = nullptr;          // [2 layers][B][2] LossComputer partials of the whole call
   size_t train_part_n = 0;
   float* train_loss_dev = nullptr;      // [3] trajectory_loss_0, _1, sum
-  // dd_forward_samples: set for the duration of one such call. Every scene of a chunk then runs `samples` decoder
-  // scenes (one per start noise) over its one perception pass: decoder scene d = b * samples + s reads the cross-BEV
-  // map, agent K / V and ego row of scene d / samples; everything else in the trajectory head is per decoder scene.
-  int samples = 1;
-  bool want_best = false;  // also pick each scene's best candidate over its samples x Q (best_trajectory / best_index)
 
   Model(const dd_config& c, const void* blob, size_t bytes, int dev) : cfg(c), device(dev) {
     BlobIndex bx(blob, bytes);  // host only: a blob that does not parse is refused before any device call
@@ -785,14 +853,16 @@ class Model {
       ClassScope(const char*& cc, const char* v) : c(cc) { c = v; }
       ~ClassScope() { c = nullptr; }
     } cls(force_class, "value_proj");
-    launch("conv_x3", fl, [&] { launch_conv_gemm(a, st); }, &a, -1.0, "form=conv_x3");
+    launch("conv_x3", fl, [&] { return launch_conv_gemm(a, st); }, &a, -1.0, "form=conv_x3");
   }
 
   // TrajectoryHead.forward_test (:578-641) as 1 + 2 x steps x 2 launches: the DDIM start + first taps, then
   // per (step, layer) the gathered value_proj conv and the decoder megakernel (decoder_mk.hip)
-  // B = decoder scenes of this head pass, S samples each of B / S perception scenes (cross, akv, egos are theirs)
-  void traj_head_mk(int B, int S, int steps, const float* cross, float* const akv[2], float* const egos[2],
+  // B = decoder scenes of this head pass, c.samples each of B / c.samples perception scenes (cross, akv, egos are
+  // theirs)
+  void traj_head_mk(const Call& c, int B, const float* cross, float* const akv[2], float* const egos[2],
                     bool& tf_pending, int tf_scenes, const float* noise) {
+    const int S = c.samples, steps = c.steps;
     const int d = 256, Q = cfg.num_modes, P = cfg.num_poses, R = B * Q;
     const int HB = cfg.lidar_h / 4, WB = cfg.lidar_w / 4, MR = R * P * 4;
     const bool vanilla = schedule == DD_SCHED_VANILLA;
@@ -821,7 +891,7 @@ class Model {
       ia.counts = counts_of(0, 0);
       ia.sa = vanilla ? 0.0f : std::sqrt(a8);
       ia.s1a = vanilla ? 1.0f : std::sqrt(1.0f - a8);
-      if (train) {  // forward_train: per-scene timesteps (train_time_film)
+      if (c.train) {  // training call: per-scene timesteps (train_time_film)
         ia.sa_b = bufs.at("train_sa").first;
         ia.s1a_b = bufs.at("train_s1a").first;
       }
@@ -865,7 +935,7 @@ class Model {
         m.slots = slots_of(si, l);
         m.akv = akv[l];
         m.ego = egos[l];
-        if (train) {
+        if (c.train) {
           m.film = bufs.at("train_film_l" + std::to_string(l)).first;
           m.film_stride = 2 * d;
         } else {
@@ -917,7 +987,7 @@ class Model {
     join();  // the heads branch on the side stream
     alias("poses_reg", reg_last);
     alias("poses_cls", cls_last);
-    train_loss_partials(B);
+    train_loss_partials(c, B);
   }
 
   // ------------------------------------------------------------------ runtime helpers
@@ -1068,13 +1138,13 @@ class Model {
   }
 
   // Capture the forward into p: one single-stream graph, or (two streams) the segmented program above.
-  void capture_program(int B, int steps, bool heads, Program& p) {
+  void capture_program(const Call& c, Program& p) {
     seg_prog = &p;
     st_cap = st;
     seg_cap = sides();
     try {
       seg_begin(0);
-      forward_body(B, steps, heads);
+      forward_body(c);
       seg_end();
     } catch (...) {
       hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1107,12 +1177,18 @@ class Model {
   static const char* groups_note(int g) { return g == 4 ? "groups=4" : (g == 2 ? "groups=2" : "groups=1"); }
 
   // `note` (profiling only): appended to the launch's detail in $DDMI_LAUNCH_LOG (groups= / form=)
+  // Returns the route f returned (the conv / GEMM dispatchers' ConvRoute), else an empty one.
   template <class F>
-  void launch(const char* name, double flops, F&& f, const ConvArgs* shape = nullptr, double bytes = -1.0,
-              const char* note = nullptr) {
+  ConvRoute launch(const char* name, double flops, F&& f, const ConvArgs* shape = nullptr, double bytes = -1.0,
+                   const char* note = nullptr) {
+    ConvRoute route;
+    auto run = [&] {
+      if constexpr (std::is_void_v<decltype(f())>) f();
+      else route = f();
+    };
     if (!profiling) {
-      f();
-      return;
+      run();
+      return route;
     }
     hipEvent_t a, b;
     if (ev_pool.size() >= 2) {
@@ -1125,21 +1201,22 @@ class Model {
       DD_HIP_CHECK(hipEventCreate(&b));
     }
     DD_HIP_CHECK(hipEventRecord(a, st));
-    f();
+    run();
     DD_HIP_CHECK(hipEventRecord(b, st));
     // conv / GEMM launches are attributed to the kernel the dispatcher actually chose (or a forced class)
     if (force_class) name = force_class;
-    else if (shape) name = last_conv_kernel();
+    else if (shape) name = route.kernel;
     std::string detail;
     if (shape) {
       const ConvArgs& c = *shape;
       detail = "M=" + std::to_string((int64_t)c.Nimg * c.Ho * c.Wo) + " N=" + std::to_string(c.Cout) +
                " K=" + std::to_string(c.KH * c.KW * c.Cin) + " k=" + std::to_string(c.KH) + " s=" +
                std::to_string(c.stride) + " z=" + std::to_string(c.batch) + " HW=" + std::to_string(c.H) + "x" +
-               std::to_string(c.W) + " cfg=" + last_conv_config();  // read after f(): the dispatcher's choice
+               std::to_string(c.W) + " cfg=" + route.config;  // the dispatcher's choice
     }
     if (note) detail += (detail.empty() ? "" : " ") + std::string(note);
     pending.push_back({name, flops, bytes >= 0.0 ? bytes : (shape ? conv_algo_bytes(*shape) : 0.0), a, b, detail});
+    return route;
   }
 
   void collect() {
@@ -1243,8 +1320,7 @@ class Model {
       a.split_cap = 8 * mo;
       a.split_part = buf(in_side ? "x3_split_side" : "x3_split_main", (size_t)a.split_cap);
     }
-    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { launch_conv_gemm(a, st); }, &a);
-    pool_done = a.pool_out && last_conv_pooled();
+    pool_done = launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a).pooled;
   }
   // timm stem conv1 / bn1 / act1 + maxpool 3x3/2: one fused kernel (stem_pool.hip) in f16x3 mode,
   // otherwise the conv into `stem` and the pool from it
@@ -1256,7 +1332,6 @@ class Model {
     const int hs = (H + 2 * c.pad - c.k) / c.stride + 1, ws = (Wd + 2 * c.pad - c.k) / c.stride + 1;
     ConvArgs a = conv_args(c, in4, (int64_t)H * Wd * c.cin, (int64_t)Wd * c.cin, c.cin, N, H, Wd, stem,
                            (int64_t)hs * ws * c.cout, (int64_t)ws * c.cout, c.cout, true, nullptr, 0, 0, 0);
-    bool done = false;
     const double fl = 2.0 * N * hs * ws * (double)c.cout * c.k * c.k * c.cin_real;
     const bool nchw = use_nchw_stem();
     // byte model: the input once at its element size (the NHWC4 copy has 4 floats per pixel, the NCHW tensor in_c;
@@ -1264,11 +1339,11 @@ class Model {
     const double in_bytes = nchw ? (double)N * H * Wd * in_c * (in_u8 ? 1.0 : 4.0) : (double)N * H * Wd * c.cin * 4.0;
     const double wb = (a.wh && a.prec == 1) ? 2.0 : 4.0;
     const double bytes = in_bytes + 4.0 * N * hp * wp * c.cout + wb * (double)c.cout * c.k * c.k * c.cin;
-    launch("stem_pool", fl, [&] {
-      done = launch_stem_pool(a, pool, hp, wp, st, nchw ? in_tab + in_idx : nullptr, nchw ? in_c : 0,
+    const ConvRoute r = launch("stem_pool", fl, [&] {
+      return launch_stem_pool(a, pool, hp, wp, st, nchw ? in_tab + in_idx : nullptr, nchw ? in_c : 0,
                               nchw ? in_u8 : 0, lut);
     }, nullptr, bytes);
-    if (done) return;
+    if (r.kernel) return;
     if (nchw) throw std::runtime_error("stem: the NCHW-input fused stem refused this shape (DDMI_STEM_NCHW=0 avoids it)");
     conv_c(c, in4, N, H, Wd, stem, true);
     launch("pool", 0, [&] { launch_maxpool3x3s2(stem, pool, N, hs, ws, c.cout, hp, wp, st); });
@@ -1316,7 +1391,7 @@ class Model {
     a.relu = relu;
     use_split(a, L.x3);
     const double fl = 2.0 * G * R * (double)L.nout * L.nin;
-    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { launch_conv_gemm(a, st); }, &a);
+    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a);
   }
 
   // C = A W^T + bias + res, and (when the GEMM can fuse it: conv_x3's quad epilogue with one N tile per row, Cout 64
@@ -1353,12 +1428,7 @@ class Model {
       a.ln_b = W(p.b);
     }
     const double fl = 2.0 * M * (double)L.nout * L.nin;
-    bool fused = false;
-    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] {
-      launch_conv_gemm(a, st);
-      fused = a.ln_out && last_conv_ln();
-    }, &a);
-    return fused;
+    return launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a).ln;
   }
 
   // C = A[:, 0:kn] W[:, k0:k0+kn]^T (+bias when with_bias) (+res) (relu): a K-slice of a Linear (the weight
@@ -1396,7 +1466,7 @@ class Model {
       if (L.x3.lo != kNone) a.wl += k0;
     }
     const double fl = 2.0 * G * R * (double)L.nout * kn;
-    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { launch_conv_gemm(a, st); }, &a);
+    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a);
   }
 
   void ln(const LNp& p, const float* x, int64_t ldx, float* y, int64_t ldy, int rows, const float* res = nullptr,
@@ -1632,22 +1702,6 @@ class Model {
     ~ModeScope() { m->gemm_mode = saved; }
   };
 
-  struct Outs {
-    float* traj = nullptr;
-    float* modes = nullptr;
-    float* cls = nullptr;
-    float* sem = nullptr;
-    float* ag_states = nullptr;
-    float* ag_labels = nullptr;
-    // forward_train: every layer's poses_reg / poses_cls and LossComputer partials ([B][2] per layer)
-    float* reg_l[2] = {nullptr, nullptr};
-    float* cls_l[2] = {nullptr, nullptr};
-    float* part_l[2] = {nullptr, nullptr};
-    // forward_samples: the scene's best candidate over its S x Q
-    float* best_traj = nullptr;
-    int* best_idx = nullptr;
-  };
-
   // denoise timesteps. truncated: roll_timesteps = round(arange(steps) * step_span / steps)[::-1]
   // (:585-588; numpy round-half-even), DDIM prev = t - 1 (set_timesteps(1000), :584);
   // vanilla: diffusers "leading" set_timesteps(steps): t_i = (steps-1-i) * (1000 / steps), prev = t - ratio.
@@ -1714,8 +1768,8 @@ class Model {
   }
 
   // training head with targets: LossComputer's per-scene partials of both layers into "train_part_l*"
-  void train_loss_partials(int B) {
-    if (!train || !train_target) return;
+  void train_loss_partials(const Call& c, int B) {
+    if (!c.train || !c.target) return;
     const int Q = cfg.num_modes, P = cfg.num_poses;
     for (int l = 0; l < 2; ++l) {
       const std::string sf = "_s0l" + std::to_string(l);
@@ -1727,7 +1781,9 @@ class Model {
     }
   }
 
-  void forward_body(int B, int steps, bool heads) {
+  void forward_body(const Call& c) {
+    const int B = c.B, steps = c.steps;
+    const bool heads = c.heads();
     const int d = 256, Q = cfg.num_modes, P = cfg.num_poses;
     const int HC = cfg.cam_h, WC = cfg.cam_w, HL = cfg.lidar_h, WL = cfg.lidar_w;
     const bool nchw = use_nchw_stem();
@@ -1748,10 +1804,10 @@ class Model {
     float* pool_l = buf("lid_pool", (size_t)B * hl2 * wl2 * 64);
     fork();
     side([&] {
-      stem_and_pool(lid.stem, lid4, B, HL, WL, stem_l, pool_l, hl2, wl2, 1, cfg.lidar_channels, kinds.lid_u8 ? 2 : 0,
-                    in_lut + 256);
+      stem_and_pool(lid.stem, lid4, B, HL, WL, stem_l, pool_l, hl2, wl2, 1, cfg.lidar_channels,
+                    c.kinds.lid_u8 ? 2 : 0, in_lut + 256);
     });
-    stem_and_pool(img.stem, cam4, B, HC, WC, stem_i, pool_i, hi2, wi2, 0, 3, kinds.cam_u8 ? 1 : 0, in_lut);
+    stem_and_pool(img.stem, cam4, B, HC, WC, stem_i, pool_i, hi2, wi2, 0, 3, c.kinds.cam_u8 ? 1 : 0, in_lut);
 
     // ---- 4 scales: trunk stages (image on the main stream, LiDAR beside it) + GPT fusion
     float* xi = pool_i;
@@ -1771,7 +1827,7 @@ class Model {
     alias("bev_feature", xl);  // (B, 8, 8, 512) NHWC; transformer_decoder_join -> fused = lidar (:204-205)
     // everything past the backbone runs in the head arithmetic (bf16 mode: f16x3; see head_mode)
     ModeScope head_scope(this, head_mode());
-    if (train) train_time_film(B);
+    if (c.train) train_time_film(B);
 
     // ---- BEV tokens + status -> keyval (B, 65, 256) (+= _keyval_embedding)
     float* KV = buf("keyval", (size_t)B * 65 * d);
@@ -1988,7 +2044,7 @@ class Model {
     // chunk's scenes in consecutive ranges of at most max_chunk / S, all S samples of a range in one pass, so that
     // no pass sees more than max_chunk decoder scenes. The named buffers keep the last pass; with several passes
     // each pass's results are gathered into "samples_*" (kernel launches: the captured forward has no copy nodes).
-    const int S = samples, npass = head_passes(B), per = (B + npass - 1) / npass;
+    const int S = c.samples, npass = head_passes(B, S), per = (B + npass - 1) / npass;
     float* all_traj = nullptr;
     float* all_reg = nullptr;
     float* all_cls = nullptr;
@@ -2011,9 +2067,9 @@ class Model {
         vals_p[l] = vals[l] ? vals[l] + (size_t)b0 * HB * WB * d : nullptr;
       }
       if (decoder_mk && mk_ready && gathered)
-        traj_head_mk(D, S, steps, cross_p, akv_p, egos_p, tf_pending, B, noise_p);
+        traj_head_mk(c, D, cross_p, akv_p, egos_p, tf_pending, B, noise_p);
       else
-        traj_head_chain(D, S, steps, cross_p, akv_p, egos_p, vals_p, gathered, tf_pending, noise_p);
+        traj_head_chain(c, D, cross_p, akv_p, egos_p, vals_p, gathered, tf_pending, noise_p);
       if (npass > 1) {
         const size_t d0 = (size_t)b0 * S;
         launch("misc", 0, [&] {
@@ -2027,7 +2083,7 @@ class Model {
         });
       }
     }
-    if (want_best) {
+    if (c.want_best()) {
       // the scene's best candidate over its S x Q: one launch after the last head pass
       const float* cls_all = npass > 1 ? all_cls : bufs.at("cls" + last_sfx).first;
       const float* reg_all = npass > 1 ? all_reg : bufs.at("reg" + last_sfx).first;
@@ -2037,17 +2093,18 @@ class Model {
     }
   }
 
-  // head passes of a chunk of B scenes at the current samples count (1 unless B * samples exceeds max_chunk)
-  int head_passes(int B) const {
-    const int per_max = std::max(1, max_chunk / samples);
+  // head passes of a chunk of B scenes with S samples each (1 unless B * S exceeds max_chunk)
+  int head_passes(int B, int S) const {
+    const int per_max = std::max(1, max_chunk / S);
     return (B + per_max - 1) / per_max;
   }
 
   // The unfused trajectory head (every config the megakernel is not specialised for, the fp32 mode, DDMI_DECODER_MK=0):
   // D = decoder scenes of this pass, S samples each of D / S perception scenes, whose cross map, value maps (dense
   // form), agent K / V and ego rows the pointers name
-  void traj_head_chain(int D, int S, int steps, const float* cross, float* const akv[2], float* const egos[2],
+  void traj_head_chain(const Call& c, int D, const float* cross, float* const akv[2], float* const egos[2],
                        float* const vals[2], bool gathered, bool& tf_pending, const float* noise) {
+    const int S = c.samples, steps = c.steps;
     const int d = 256, Q = cfg.num_modes, P = cfg.num_poses, R = D * Q;
     const int HB = cfg.lidar_h / 4, WB = cfg.lidar_w / 4;
     float* imgx = buf("ddim_img", (size_t)R * P * 2);
@@ -2057,7 +2114,7 @@ class Model {
       // vanilla (C5 ablation): x_T = noise (sa = 0, s1a = 1 keep it bit-exact)
       const float a8 = ac[cfg.trunc_timestep];
       const float sa = vanilla ? 0.0f : std::sqrt(a8), s1a = vanilla ? 1.0f : std::sqrt(1.0f - a8);
-      if (train)  // forward_train: per-scene timesteps (train_time_film)
+      if (c.train)  // training call: per-scene timesteps (train_time_film)
         launch("misc", 0, [&] {
           launch_train_noisy(W(anchor), noise, bufs.at("train_sa").first, bufs.at("train_s1a").first, imgx, D, Q * P,
                              st);
@@ -2125,7 +2182,7 @@ class Model {
         a.rowmap = rows;
         a.rowmap_nimg = D / S;  // the images of `cross`; the rows are the D decoder scenes' taps
         const double fl = 2.0 * MR * (double)d * 9 * dl[l].vproj.cin_real;
-        launch("conv_x3", fl, [&] { launch_conv_gemm(a, st); }, &a);
+        launch("conv_x3", fl, [&] { return launch_conv_gemm(a, st); }, &a);
         vrows_l[l] = vrows;
       };
       if (gathered) {
@@ -2183,7 +2240,7 @@ class Model {
         // ffn -> norm3 -> FiLM time modulation
         gemm(w.ffn0, x3, d, R, hf, 1024, true);
         gemm(w.ffn2, hf, 1024, R, x2, d);
-        if (train) {  // one FiLM vector per scene (its Q rows)
+        if (c.train) {  // one FiLM vector per scene (its Q rows)
           const float* fl = bufs.at("train_film_l" + std::to_string(l)).first;
           ln(w.n3, x2, d, x2, d, R, nullptr, 0, 1, fl, fl + d, Q, 2 * d);
         } else {
@@ -2221,60 +2278,59 @@ class Model {
     launch("misc", 0, [&] { launch_select_mode(cls_last, reg_last, traj, idx, D, Q, P, st); });
     alias("poses_reg", reg_last);
     alias("poses_cls", cls_last);
-    train_loss_partials(D);
+    train_loss_partials(c, D);
   }
 
   std::map<std::string, float*> aliases;
   void alias(const std::string& name, float* p) { aliases[name] = p; }
 
-  // noise == NULL: draw it on the device, draw blocks [block0, block0 + B * samples) of the handle's stream (a
+  // c.noise == NULL: draw it on the device, draw blocks [block0, block0 + B * samples) of the handle's stream (a
   // block = the Q * P * 2 normals of one decoder scene; sample s of the chunk's scene b takes block0 + b * samples + s)
-  // camera / lidar: fp32 NCHW or uint8 (kinds)
-  void stage_inputs(const void* camera, const void* lidar, const float* status, const float* noise, int B,
-                    uint64_t block0) {
+  void stage_inputs(const Call& c, uint64_t block0) {
+    const int B = c.B;
     float* st_in = buf("in_status", (size_t)B * 8);
     const size_t blk = (size_t)cfg.num_modes * cfg.num_poses * 2;
-    const size_t per = blk * (size_t)samples;  // noise floats per scene
+    const size_t per = blk * (size_t)c.samples;  // noise floats per scene
     float* nz = buf("in_noise", (size_t)B * per);
-    if (kinds.lid_u8 && lut_hist_max != kinds.hist_max) {
+    if (c.kinds.lid_u8 && lut_hist_max != c.kinds.hist_max) {
       // a small launch on the stream ahead of the forward (never a node of a captured graph): the handle's earlier
       // forwards, which read the table, are ordered before this one (OnStream)
-      launch("misc", 0, [&] { launch_lidar_lut(in_lut + 256, kinds.hist_max, st); });
-      lut_hist_max = kinds.hist_max;
+      launch("misc", 0, [&] { launch_lidar_lut(in_lut + 256, c.kinds.hist_max, st); });
+      lut_hist_max = c.kinds.hist_max;
     }
     if (use_nchw_stem()) {
       // the stems read the caller's NCHW tensors in place: only their addresses go to the device table (the
       // captured graph reads them from there); the caller's buffers outlive the forward (stream order)
-      launch("misc", 0, [&] { launch_set_ptrs(in_tab, camera, lidar, st); });
+      launch("misc", 0, [&] { launch_set_ptrs(in_tab, c.camera, c.lidar, st); });
     } else {
       float* cam4 = buf("in_cam4", (size_t)B * cfg.cam_h * cfg.cam_w * 4);
       float* lid4 = buf("in_lid4", (size_t)B * cfg.lidar_h * cfg.lidar_w * 4);
       launch("misc", 0, [&] {
-        if (kinds.cam_u8)
-          launch_u8_to_nhwc4(static_cast<const uint8_t*>(camera), cam4, B, 3, cfg.cam_h, cfg.cam_w, 1, in_lut, st);
+        if (c.kinds.cam_u8)
+          launch_u8_to_nhwc4(static_cast<const uint8_t*>(c.camera), cam4, B, 3, cfg.cam_h, cfg.cam_w, 1, in_lut, st);
         else
-          launch_nchw_to_nhwc(static_cast<const float*>(camera), cam4, B, 3, cfg.cam_h, cfg.cam_w, 4, st);
+          launch_nchw_to_nhwc(static_cast<const float*>(c.camera), cam4, B, 3, cfg.cam_h, cfg.cam_w, 4, st);
       });
       launch("misc", 0, [&] {
-        if (kinds.lid_u8)
-          launch_u8_to_nhwc4(static_cast<const uint8_t*>(lidar), lid4, B, cfg.lidar_channels, cfg.lidar_h, cfg.lidar_w, 0,
-                             in_lut + 256, st);
+        if (c.kinds.lid_u8)
+          launch_u8_to_nhwc4(static_cast<const uint8_t*>(c.lidar), lid4, B, cfg.lidar_channels, cfg.lidar_h,
+                             cfg.lidar_w, 0, in_lut + 256, st);
         else
-          launch_nchw_to_nhwc(static_cast<const float*>(lidar), lid4, B, cfg.lidar_channels, cfg.lidar_h, cfg.lidar_w, 4,
-                              st);
+          launch_nchw_to_nhwc(static_cast<const float*>(c.lidar), lid4, B, cfg.lidar_channels, cfg.lidar_h,
+                              cfg.lidar_w, 4, st);
       });
     }
-    DD_HIP_CHECK(hipMemcpyAsync(st_in, status, sizeof(float) * B * 8, hipMemcpyDeviceToDevice, st));
-    if (train) {
+    DD_HIP_CHECK(hipMemcpyAsync(st_in, c.status, sizeof(float) * B * 8, hipMemcpyDeviceToDevice, st));
+    if (c.train) {
       float* tb = buf("in_tsteps", (size_t)B);
-      DD_HIP_CHECK(hipMemcpyAsync(tb, train_t, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
-      if (train_target) {
+      DD_HIP_CHECK(hipMemcpyAsync(tb, c.timesteps, sizeof(int) * B, hipMemcpyDeviceToDevice, st));
+      if (c.target) {
         float* tg = buf("in_target", (size_t)B * cfg.num_poses * 3);
-        DD_HIP_CHECK(hipMemcpyAsync(tg, train_target, sizeof(float) * B * cfg.num_poses * 3, hipMemcpyDeviceToDevice, st));
+        DD_HIP_CHECK(hipMemcpyAsync(tg, c.target, sizeof(float) * B * cfg.num_poses * 3, hipMemcpyDeviceToDevice, st));
       }
     }
-    if (noise)
-      DD_HIP_CHECK(hipMemcpyAsync(nz, noise, sizeof(float) * B * per, hipMemcpyDeviceToDevice, st));
+    if (c.noise)
+      DD_HIP_CHECK(hipMemcpyAsync(nz, c.noise, sizeof(float) * B * per, hipMemcpyDeviceToDevice, st));
     else
       launch("misc", 0, [&] { launch_normal_philox(nz, (int64_t)(B * per), rng_seed, block0 * blk, st); });
   }
@@ -2290,46 +2346,17 @@ class Model {
     DD_HIP_CHECK(hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, st));
   }
 
-  // The forward of B scenes. More than max_chunk scenes run as ceil(B / max_chunk) equal chunks (the last one
-  // may be shorter) through the same per-chunk path, in order on the handle's stream; every kernel of the path
-  // is per scene, so a chunked forward equals the forward of its chunks scene for scene.
-  // camera / lidar: fp32 or uint8 as `kinds` says (chunk offsets are in bytes of the input's element type)
-  void forward(const void* camera, const void* lidar, const float* status, const float* noise, int B, int steps,
-               const Outs& o, hipStream_t caller) {
-    if (B <= 0) throw std::invalid_argument("batch must be positive");
-    if (steps <= 0 || steps > (schedule == DD_SCHED_VANILLA ? 1000 : cfg.step_span))
-      throw std::invalid_argument("steps must be in [1, step_span] (truncated) or [1, 1000] (vanilla)");
-    if (!camera || !lidar || !status || !o.traj) throw std::invalid_argument("null input/output pointer");
-    if (!noise && (cfg.num_modes * cfg.num_poses) % 2)
-      throw std::invalid_argument("device noise draw needs num_modes * num_poses even");
-    const int Q = cfg.num_modes, P = cfg.num_poses;
-    const int nch = (B + max_chunk - 1) / max_chunk, chunk = (B + nch - 1) / nch;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-      const int n = std::min(chunk, B - b0);
-      auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-      auto offb = [&](const void* p, size_t per, size_t esz) {
-        return static_cast<const void*>(static_cast<const char*>(p) + (size_t)b0 * per * esz);
-      };
-      auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-      Outs oc;
-      oc.traj = offw(o.traj, (size_t)P * 3);
-      oc.modes = offw(o.modes, (size_t)Q * P * 3);
-      oc.cls = offw(o.cls, (size_t)Q);
-      oc.sem = offw(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
-      oc.ag_states = offw(o.ag_states, (size_t)30 * 5);
-      oc.ag_labels = offw(o.ag_labels, (size_t)30);
-      forward_chunk(offb(camera, (size_t)3 * cfg.cam_h * cfg.cam_w, cam_esz()),
-                    offb(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w, lid_esz()), off(status, 8),
-                    off(noise, (size_t)Q * P * 2), n, steps, oc, caller, rng_next + (uint64_t)b0);
-    }
-    if (!noise) rng_next += (uint64_t)B;
-  }
-
-  // S trajectory samples per scene over one perception pass (dd_forward_samples): the scene chunks of forward(), the
-  // backbone at the chunk's full batch, the trajectory head over decoder scenes d = b * S + s in passes of at most
-  // max_chunk of them (forward_body). noise (B,S,Q,P,2) or nullptr: draw blocks [rng_next, rng_next + B * S).
-  void forward_samples(const void* camera, const void* lidar, const float* status, const float* noise, int B, int S,
-                       int steps, const Outs& o, hipStream_t caller) {
+  // One forward call of any kind, B scenes. More than max_chunk scenes run as ceil(B / max_chunk) equal chunks (the
+  // last one may be shorter) through the same per-chunk path, in order on the handle's stream; every kernel of the
+  // path is per scene, so a chunked forward equals the forward of its chunks scene for scene.
+  // - samples = S > 1 (dd_forward_samples): the backbone at the chunk's full batch, the trajectory head over decoder
+  //   scenes d = b * S + s in passes of at most max_chunk of them (forward_body). noise (B,S,Q,P,2) or nullptr: draw
+  //   blocks [rng_next, rng_next + B * S).
+  // - train (dd_forward_train, transfuser_model_v2.py:520-576): the training-mode head over the eval-mode network as a
+  //   loss evaluator: per-scene timesteps / noise in, every layer's poses out, and with targets the LossComputer
+  //   losses (multimodal_loss.py:119-168) of both layers and their sum, reduced over the whole batch after its chunks.
+  void forward(Call c, hipStream_t caller) {
+    const int B = c.B, S = c.samples, Q = cfg.num_modes, P = cfg.num_poses;
     if (S < 1 || S > DD_MAX_SAMPLES)
       throw std::invalid_argument("dd_forward_samples: S must be in [1, " + std::to_string(DD_MAX_SAMPLES) + "], got " +
                                   std::to_string(S));
@@ -2337,102 +2364,33 @@ class Model {
       throw std::invalid_argument("dd_forward_samples: S = " + std::to_string(S) + " exceeds the handle's chunk limit " +
                                   "(max_chunk = " + std::to_string(max_chunk) + " decoder scenes per head pass)");
     if (B <= 0) throw std::invalid_argument("batch must be positive");
-    if (steps <= 0 || steps > (schedule == DD_SCHED_VANILLA ? 1000 : cfg.step_span))
+    if (c.steps <= 0 || c.steps > (schedule == DD_SCHED_VANILLA ? 1000 : cfg.step_span))
       throw std::invalid_argument("steps must be in [1, step_span] (truncated) or [1, 1000] (vanilla)");
-    if (!camera || !lidar || !status || !o.traj) throw std::invalid_argument("null input/output pointer");
-    if (!noise && (cfg.num_modes * cfg.num_poses) % 2)
-      throw std::invalid_argument("device noise draw needs num_modes * num_poses even");
-    struct Reset {
-      Model& m;
-      ~Reset() {
-        m.samples = 1;
-        m.want_best = false;
-      }
-    } reset{*this};
-    samples = S;
-    want_best = o.best_traj || o.best_idx;
-    const int Q = cfg.num_modes, P = cfg.num_poses;
-    const int nch = (B + max_chunk - 1) / max_chunk, chunk = (B + nch - 1) / nch;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-      const int n = std::min(chunk, B - b0);
-      auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-      auto offb = [&](const void* p, size_t per, size_t esz) {
-        return static_cast<const void*>(static_cast<const char*>(p) + (size_t)b0 * per * esz);
-      };
-      auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-      Outs oc;
-      oc.traj = offw(o.traj, (size_t)S * P * 3);
-      oc.modes = offw(o.modes, (size_t)S * Q * P * 3);
-      oc.cls = offw(o.cls, (size_t)S * Q);
-      oc.best_traj = offw(o.best_traj, (size_t)P * 3);
-      oc.best_idx = o.best_idx ? o.best_idx + b0 : nullptr;
-      oc.sem = offw(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
-      oc.ag_states = offw(o.ag_states, (size_t)30 * 5);
-      oc.ag_labels = offw(o.ag_labels, (size_t)30);
-      forward_chunk(offb(camera, (size_t)3 * cfg.cam_h * cfg.cam_w, cam_esz()),
-                    offb(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w, lid_esz()), off(status, 8),
-                    off(noise, (size_t)S * Q * P * 2), n, steps, oc, caller, rng_next + (uint64_t)b0 * S);
-    }
-    if (!noise) rng_next += (uint64_t)B * S;
-  }
-
-  // The training-mode trajectory head (forward_train, transfuser_model_v2.py:520-576) over the eval-mode network, as
-  // a loss evaluator: per-scene timesteps / noise in, every layer's poses out, and with targets the LossComputer losses
-  // (multimodal_loss.py:119-168) of both layers and their sum (loss[3]), reduced over the whole batch after its chunks.
-  void forward_train(const void* camera, const void* lidar, const float* status, const float* noise,
-                     const int* timesteps, const float* target, int B, const Outs& o, float* loss, float cls_w,
-                     float reg_w, hipStream_t caller) {
-    if (B <= 0) throw std::invalid_argument("batch must be positive");
-    if (!camera || !lidar || !status || !noise || !timesteps || !o.traj)
+    const bool null_io = !c.camera || !c.lidar || !c.status || !c.o.traj;
+    if (c.train && (null_io || !c.noise || !c.timesteps))
       throw std::invalid_argument("dd_forward_train: null input / output pointer (noise and timesteps are required)");
-    if (loss && !target) throw std::invalid_argument("dd_forward_train: loss requested without targets");
-    const int Q = cfg.num_modes, P = cfg.num_poses;
-    if (target && train_part_n < (size_t)B) {
+    if (null_io) throw std::invalid_argument("null input/output pointer");
+    if (!c.noise && (Q * P) % 2) throw std::invalid_argument("device noise draw needs num_modes * num_poses even");
+    if (c.loss && !c.target) throw std::invalid_argument("dd_forward_train: loss requested without targets");
+    if (c.target && train_part_n < (size_t)B) {
       DD_HIP_CHECK(hipDeviceSynchronize());  // an earlier call's reduction may still read the old buffer
       if (train_part) DD_HIP_CHECK(hipFree(train_part));
       train_part = nullptr;
       DD_HIP_CHECK(hipMalloc(&train_part, sizeof(float) * 4 * (size_t)B));
       train_part_n = (size_t)B;
     }
-    struct Reset {
-      Model& m;
-      ~Reset() {
-        m.train = false;
-        m.train_t = nullptr;
-        m.train_target = nullptr;
-      }
-    } reset{*this};
-    train = true;
+    for (int l = 0; l < 2; ++l) c.o.part_l[l] = c.target ? train_part + (size_t)l * 2 * B : nullptr;
     const int nch = (B + max_chunk - 1) / max_chunk, chunk = (B + nch - 1) / nch;
-    for (int b0 = 0; b0 < B; b0 += chunk) {
-      const int n = std::min(chunk, B - b0);
-      auto off = [&](const float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-      auto offb = [&](const void* p, size_t per, size_t esz) {
-        return static_cast<const void*>(static_cast<const char*>(p) + (size_t)b0 * per * esz);
-      };
-      auto offw = [&](float* p, size_t per) { return p ? p + (size_t)b0 * per : nullptr; };
-      Outs oc;
-      oc.traj = offw(o.traj, (size_t)P * 3);
-      oc.sem = offw(o.sem, (size_t)7 * (cfg.lidar_h / 2) * cfg.lidar_w);
-      oc.ag_states = offw(o.ag_states, (size_t)30 * 5);
-      oc.ag_labels = offw(o.ag_labels, (size_t)30);
-      for (int l = 0; l < 2; ++l) {
-        oc.reg_l[l] = o.reg_l[l] ? o.reg_l[l] + (size_t)b0 * Q * P * 3 : nullptr;
-        oc.cls_l[l] = o.cls_l[l] ? o.cls_l[l] + (size_t)b0 * Q : nullptr;
-        oc.part_l[l] = target ? train_part + (size_t)l * 2 * B + (size_t)b0 * 2 : nullptr;
-      }
-      train_t = timesteps + b0;
-      train_target = target ? target + (size_t)b0 * P * 3 : nullptr;
-      forward_chunk(offb(camera, (size_t)3 * cfg.cam_h * cfg.cam_w, cam_esz()),
-                    offb(lidar, (size_t)cfg.lidar_channels * cfg.lidar_h * cfg.lidar_w, lid_esz()), off(status, 8),
-                    off(noise, (size_t)Q * P * 2), n, 1, oc, caller, 0);
-    }
-    if (target) {
+    for (int b0 = 0; b0 < B; b0 += chunk)
+      forward_chunk(c.chunk(cfg, b0, std::min(chunk, B - b0)), caller, rng_next + (uint64_t)b0 * S);
+    if (!c.noise) rng_next += (uint64_t)B * S;  // never a training call: it brings its noise
+    if (c.target) {
       // the batch means of both layers and their sum, on the caller's stream (every chunk handed back to it)
-      launch_traj_loss_reduce(train_part, train_loss_dev, B, Q, P, cls_w, reg_w, caller);
-      launch_traj_loss_reduce(train_part + 2 * (size_t)B, train_loss_dev + 1, B, Q, P, cls_w, reg_w, caller);
+      launch_traj_loss_reduce(train_part, train_loss_dev, B, Q, P, c.cls_w, c.reg_w, caller);
+      launch_traj_loss_reduce(train_part + 2 * (size_t)B, train_loss_dev + 1, B, Q, P, c.cls_w, c.reg_w, caller);
       launch_add2(train_loss_dev, caller);
-      if (loss) DD_HIP_CHECK(hipMemcpyAsync(loss, train_loss_dev, 3 * sizeof(float), hipMemcpyDeviceToDevice, caller));
+      if (c.loss)
+        DD_HIP_CHECK(hipMemcpyAsync(c.loss, train_loss_dev, 3 * sizeof(float), hipMemcpyDeviceToDevice, caller));
       // the reduction read the handle-wide partials: the handle's next forward waits for it (OnStream)
       DD_HIP_CHECK(hipEventRecord(ev_out, caller));
     }
@@ -2464,22 +2422,20 @@ class Model {
     }
   };
 
-  void forward_chunk(const void* camera, const void* lidar, const float* status, const float* noise, int B,
-                     int steps, const Outs& o, hipStream_t caller, uint64_t scene0) {
+  void forward_chunk(const Call& c, hipStream_t caller, uint64_t block0) {
+    const int B = c.B, steps = c.steps;
+    const Outs& o = c.o;
     DD_HIP_CHECK(hipSetDevice(device));
     DD_TRACE("forward_chunk B=%d steps=%d caller=%p use_side=%d", B, steps, (void*)caller, (int)use_side);
     OnStream on(*this, caller);
-    const bool heads = o.sem || o.ag_states || o.ag_labels;
+    const bool heads = c.heads();
     const uint64_t gen0 = generation;
-    stage_inputs(camera, lidar, status, noise, B, scene0);
+    stage_inputs(c, block0);
     DD_TRACE("staged");
     ensure_film(steps);
     DD_TRACE("film");
     if (generation != gen0) known_shapes.clear();
-    const std::string key = std::to_string(B) + "/" + std::to_string(steps) + "/" + std::to_string(heads) + "/g" +
-                            std::to_string(gemm_mode) + "/s" + std::to_string(schedule) +
-                            (train ? (train_target ? "/train1" : "/train0") : "") + "/x" + std::to_string(samples) +
-                            (want_best ? "/best" : "") + "/i" + (kinds.cam_u8 ? "b" : "f") + (kinds.lid_u8 ? "b" : "f");
+    const std::string key = c.key() + "/g" + std::to_string(gemm_mode) + "/s" + std::to_string(schedule);
     if (use_graph && !profiling && known_shapes.count(key)) {
       if (graph_gen != generation || programs.size() > 8) {
         // an earlier replay may still run (on the caller's stream in direct mode): ev_out marks the last forward
@@ -2491,7 +2447,7 @@ class Model {
       DD_TRACE("graph key %s cached=%d", key.c_str(), (int)(it != programs.end()));
       if (it == programs.end()) {
         Program p;
-        capture_program(B, steps, heads, p);
+        capture_program(c, p);
         DD_TRACE("captured %d segments (model %p)", p.segments, (void*)this);
         it = programs.emplace(key, std::move(p)).first;
       }
@@ -2501,17 +2457,17 @@ class Model {
       // eager run (the first call for a shape allocates every buffer; later calls are captured)
       const uint64_t gen1 = generation;
       DD_TRACE("eager");
-      forward_body(B, steps, heads);
+      forward_body(c);
       DD_TRACE("eager done");
       if (generation != gen1) known_shapes.clear();
       known_shapes.insert(key);
     }
     const int Q = cfg.num_modes, P = cfg.num_poses;
     DD_TRACE("copy out");
-    if (samples > 1) {
+    if (c.samples > 1) {
       // by buffer name (the aliases are the last eager pass's): the last pass's buffers, or the gathered passes
-      const size_t D = (size_t)B * samples;
-      const bool multi = head_passes(B) > 1;
+      const size_t D = (size_t)B * c.samples;
+      const bool multi = head_passes(B, c.samples) > 1;
       const std::string sf = "_s" + std::to_string(steps - 1) + "l1";
       copy_out(o.traj, multi ? "samples_trajectory" : "trajectory", D * P * 3);
       copy_out(o.modes, multi ? "samples_reg" : "reg" + sf, D * Q * P * 3);
@@ -2521,7 +2477,7 @@ class Model {
       copy_out(o.modes, "poses_reg", (size_t)B * Q * P * 3);
       copy_out(o.cls, "poses_cls", (size_t)B * Q);
     }
-    if (want_best) {
+    if (c.want_best()) {
       copy_out(o.best_traj, "best_trajectory", (size_t)B * P * 3);
       copy_out(reinterpret_cast<float*>(o.best_idx), "best_index", (size_t)B);
     }
@@ -2530,12 +2486,12 @@ class Model {
       copy_out(o.ag_states, "agent_states", (size_t)B * 30 * 5);
       copy_out(o.ag_labels, "agent_labels", (size_t)B * 30);
     }
-    if (train) {
+    if (c.train) {
       for (int l = 0; l < 2; ++l) {
         const std::string sf = "_s0l" + std::to_string(l);
         copy_out(o.reg_l[l], "reg" + sf, (size_t)B * Q * P * 3);
         copy_out(o.cls_l[l], "cls" + sf, (size_t)B * Q);
-        if (train_target) copy_out(o.part_l[l], "train_part_l" + std::to_string(l), (size_t)B * 2);
+        if (c.target) copy_out(o.part_l[l], "train_part_l" + std::to_string(l), (size_t)B * 2);
       }
     }
     // ev_out marks the end of this forward on whichever stream it ran (dd_numerics_flags / dd_tap wait for it)
@@ -2597,14 +2553,10 @@ static int guarded(F&& f) {
 
 // ---- inputs: every forward entry point goes through a dd_inputs descriptor (the float-pointer entries fill one)
 namespace {
-struct InDesc {
-  const void* cam = nullptr;
-  const void* lid = nullptr;
-  ddmi::Model::InKinds kinds;
-};
-// Exactly one pointer per sensor, hist_max in 1..255 with a uint8 LiDAR: checked before any device work, the
-// offending field named.
-InDesc check_inputs(const char* who, const dd_inputs* in) {
+// The call's inputs, and the outputs common to the three output structs. Exactly one pointer per sensor, hist_max in
+// 1..255 with a uint8 LiDAR: checked before any device work, the offending field named.
+template <class O>
+Model::Call make_call(const char* who, const dd_inputs* in, int B, int steps, const O& outs) {
   if (!in) throw std::invalid_argument(std::string(who) + ": null inputs descriptor");
   auto one = [&](const void* f, const void* u, const char* nf, const char* nu) {
     if ((f != nullptr) == (u != nullptr))
@@ -2613,25 +2565,27 @@ InDesc check_inputs(const char* who, const dd_inputs* in) {
   };
   one(in->camera_f32, in->camera_u8, "camera_f32", "camera_u8");
   one(in->lidar_f32, in->lidar_u8, "lidar_f32", "lidar_u8");
-  InDesc d;
-  d.kinds.cam_u8 = in->camera_u8 != nullptr;
-  d.kinds.lid_u8 = in->lidar_u8 != nullptr;
-  d.cam = d.kinds.cam_u8 ? static_cast<const void*>(in->camera_u8) : in->camera_f32;
-  d.lid = d.kinds.lid_u8 ? static_cast<const void*>(in->lidar_u8) : in->lidar_f32;
-  if (d.kinds.lid_u8) {
+  Model::Call c;
+  c.kinds.cam_u8 = in->camera_u8 != nullptr;
+  c.kinds.lid_u8 = in->lidar_u8 != nullptr;
+  c.camera = c.kinds.cam_u8 ? static_cast<const void*>(in->camera_u8) : in->camera_f32;
+  c.lidar = c.kinds.lid_u8 ? static_cast<const void*>(in->lidar_u8) : in->lidar_f32;
+  if (c.kinds.lid_u8) {
     if (in->lidar_hist_max < 1 || in->lidar_hist_max > 255)
       throw std::invalid_argument(std::string(who) + ": dd_inputs.lidar_hist_max = " +
                                   std::to_string(in->lidar_hist_max) + " is not in 1..255");
-    d.kinds.hist_max = in->lidar_hist_max;
+    c.kinds.hist_max = in->lidar_hist_max;
   }
-  return d;
+  c.status = in->status;
+  c.noise = in->noise;
+  c.B = B;
+  c.steps = steps;
+  c.o.traj = outs.trajectory;
+  c.o.sem = outs.bev_semantic_map;
+  c.o.ag_states = outs.agent_states;
+  c.o.ag_labels = outs.agent_labels;
+  return c;
 }
-// the call's input kinds on the handle for the duration of the call
-struct KindScope {
-  Model& m;
-  KindScope(Model& mm, const ddmi::Model::InKinds& k) : m(mm) { m.kinds = k; }
-  ~KindScope() { m.kinds = ddmi::Model::InKinds(); }
-};
 dd_inputs float_inputs(const float* camera, const float* lidar, const float* status, const float* noise) {
   dd_inputs in;
   std::memset(&in, 0, sizeof(in));
@@ -2700,20 +2654,14 @@ int dd_create(const dd_config* cfg, const void* blob, size_t bytes, int device, 
 int dd_forward_in(dd_handle* h, const dd_inputs* in, int B, int steps, const dd_outputs* outs, void* stream) {
   return guarded([&] {
     if (!h || !outs) throw std::invalid_argument("dd_forward_ex: null handle/outputs");
-    const InDesc d = check_inputs("dd_forward_in", in);
+    Model::Call c = make_call("dd_forward_in", in, B, steps, *outs);
+    c.o.modes = outs->poses_reg;
+    c.o.cls = outs->poses_cls;
     std::lock_guard<std::mutex> lk(h->mu);
 #ifdef DDMI_SEGV_TRACE
     signal(SIGSEGV, ddmi_segv);  // the HSA runtime may have replaced it since the library loaded
 #endif
-    Model::Outs o;
-    o.traj = outs->trajectory;
-    o.modes = outs->poses_reg;
-    o.cls = outs->poses_cls;
-    o.sem = outs->bev_semantic_map;
-    o.ag_states = outs->agent_states;
-    o.ag_labels = outs->agent_labels;
-    KindScope ks(*h->m, d.kinds);
-    h->m->forward(d.cam, d.lid, in->status, in->noise, B, steps, o, static_cast<hipStream_t>(stream));
+    h->m->forward(c, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -2727,19 +2675,14 @@ int dd_forward_samples_in(dd_handle* h, const dd_inputs* in, int B, int S, int s
                           void* stream) {
   return guarded([&] {
     if (!h || !outs) throw std::invalid_argument("dd_forward_samples: null handle/outputs");
-    const InDesc d = check_inputs("dd_forward_samples_in", in);
+    Model::Call c = make_call("dd_forward_samples_in", in, B, steps, *outs);
+    c.samples = S;
+    c.o.modes = outs->poses_reg;
+    c.o.cls = outs->poses_cls;
+    c.o.best_traj = outs->best_trajectory;
+    c.o.best_idx = outs->best_index;
     std::lock_guard<std::mutex> lk(h->mu);
-    Model::Outs o;
-    o.traj = outs->trajectory;
-    o.modes = outs->poses_reg;
-    o.cls = outs->poses_cls;
-    o.best_traj = outs->best_trajectory;
-    o.best_idx = outs->best_index;
-    o.sem = outs->bev_semantic_map;
-    o.ag_states = outs->agent_states;
-    o.ag_labels = outs->agent_labels;
-    KindScope ks(*h->m, d.kinds);
-    h->m->forward_samples(d.cam, d.lid, in->status, in->noise, B, S, steps, o, static_cast<hipStream_t>(stream));
+    h->m->forward(c, static_cast<hipStream_t>(stream));
   });
 }
 
@@ -2753,20 +2696,19 @@ int dd_forward_train_in(dd_handle* h, const dd_inputs* in, const int* timesteps,
                         float cls_weight, float reg_weight, const dd_train_outputs* outs, void* stream) {
   return guarded([&] {
     if (!h || !outs) throw std::invalid_argument("dd_forward_train: null handle/outputs");
-    const InDesc d = check_inputs("dd_forward_train_in", in);
-    std::lock_guard<std::mutex> lk(h->mu);
-    Model::Outs o;
-    o.traj = outs->trajectory;
-    o.sem = outs->bev_semantic_map;
-    o.ag_states = outs->agent_states;
-    o.ag_labels = outs->agent_labels;
+    Model::Call c = make_call("dd_forward_train_in", in, B, 1, *outs);
+    c.train = true;
+    c.timesteps = timesteps;
+    c.target = target_traj;
+    c.cls_w = cls_weight;
+    c.reg_w = reg_weight;
+    c.loss = outs->loss;
     for (int l = 0; l < 2; ++l) {
-      o.reg_l[l] = outs->poses_reg[l];
-      o.cls_l[l] = outs->poses_cls[l];
+      c.o.reg_l[l] = outs->poses_reg[l];
+      c.o.cls_l[l] = outs->poses_cls[l];
     }
-    KindScope ks(*h->m, d.kinds);
-    h->m->forward_train(d.cam, d.lid, in->status, in->noise, timesteps, target_traj, B, o, outs->loss, cls_weight,
-                        reg_weight, static_cast<hipStream_t>(stream));
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->m->forward(c, static_cast<hipStream_t>(stream));
   });
 }
 

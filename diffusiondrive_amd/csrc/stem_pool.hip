@@ -465,31 +465,31 @@ __global__ __launch_bounds__(NT, 2) void stem_pool_kernel(const float* __restric
 
 }  // namespace
 
-// Returns false when the conv is not a 7x7 / s2 / p3, Cin 4, Cout 64 f16x3 / bf16 stem on a contiguous
+// Returns kernel == nullptr when the conv is not a 7x7 / s2 / p3, Cin 4, Cout 64 f16x3 / bf16 stem on a contiguous
 // NHWC4 input (src == nullptr) or on the NCHW tensor of src_c channels whose address is the device word *src
 // (the caller then runs the conv and the pool separately). u8 = 1 / 2: *src is the uint8 (B, H, W, 3) HWC image
 // (src_c 3) / the planar uint8 (B, src_c, H, W) tensor and lut the 256 fp32 values of the bytes (device memory).
-bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st, const void* const* src,
-                      int src_c, int u8, const float* lut) {
-  if (!a.wh || (a.prec == 0 && !a.wl) || (a.prec != 0 && a.prec != 1) || !a.wsinv) return false;
+ConvRoute launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStream_t st,
+                           const void* const* src, int src_c, int u8, const float* lut) {
+  if (!a.wh || (a.prec == 0 && !a.wl) || (a.prec != 0 && a.prec != 1) || !a.wsinv) return {};
   if (a.KH != 7 || a.KW != 7 || a.stride != 2 || a.pad != 3 || a.Cin != 4 || a.Cout != 64 || a.batch != 1 || a.res ||
       !a.relu)
-    return false;
-  if (u8 < 0 || u8 > 2 || (u8 && (!src || !lut)) || (u8 == 1 && src_c != 3)) return false;
+    return {};
+  if (u8 < 0 || u8 > 2 || (u8 && (!src || !lut)) || (u8 == 1 && src_c != 3)) return {};
   if (src) {
-    if (src_c < 1 || src_c > 3 || (int64_t)a.Nimg * src_c * a.H * a.W >= (int64_t(1) << 31)) return false;
+    if (src_c < 1 || src_c > 3 || (int64_t)a.Nimg * src_c * a.H * a.W >= (int64_t(1) << 31)) return {};
   } else if (a.in_sw != 4 || a.in_sh != (int64_t)a.W * 4 || a.in_sn != (int64_t)a.H * a.W * 4) {
-    return false;
+    return {};
   }
-  if (a.ldh < 196 || a.ldh % 4) return false;
+  if (a.ldh < 196 || a.ldh % 4) return {};
   const int Hs = a.Ho, Ws = a.Wo;
-  if (Hp != (Hs + 2 - 3) / 2 + 1 || Wp != (Ws + 2 - 3) / 2 + 1) return false;
+  if (Hp != (Hs + 2 - 3) / 2 + 1 || Wp != (Ws + 2 - 3) / 2 + 1) return {};
   if ((!src && (reinterpret_cast<uintptr_t>(a.in) & 15)) || (reinterpret_cast<uintptr_t>(pool_out) & 15) ||
       (reinterpret_cast<uintptr_t>(a.wh) & 7) || (a.prec == 0 && (reinterpret_cast<uintptr_t>(a.wl) & 7)))
-    return false;
+    return {};
   const int tiles_x = (Wp + PW - 1) / PW, tiles_y = (Hp + PH - 1) / PH;
   const int64_t nt64 = (int64_t)a.Nimg * tiles_x * tiles_y;
-  if (nt64 >= (int64_t(1) << 31)) return false;
+  if (nt64 >= (int64_t(1) << 31)) return {};
   const int ntiles = (int)nt64;
   int dev = 0, cus = 256;
   DD_HIP_CHECK(hipGetDevice(&dev));
@@ -536,9 +536,8 @@ bool launch_stem_pool(const ConvArgs& a, float* pool_out, int Hp, int Wp, hipStr
     pick(std::integral_constant<int, 1>());
   else
     pick(std::integral_constant<int, 0>());
-  set_last_conv_config(a.prec == 1 ? "stem_pool<bf16>" : "stem_pool<f16x3>");
   DD_HIP_CHECK(hipGetLastError());
-  return true;
+  return {"stem_pool", a.prec == 1 ? "stem_pool<bf16>" : "stem_pool<f16x3>"};
 }
 
 }  // namespace ddmi

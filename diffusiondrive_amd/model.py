@@ -172,6 +172,74 @@ class DiffusionDriveModel:
         ins.lidar_hist_max = int(cfg.hist_max_per_pixel) if lid_u8 else 0
         return cam, lid, ins
 
+    def _stage(self, features, s, noise, draw=None, timesteps=None, target=None):
+        """Everything a forward call reads, on the device and shape-checked as far as every call kind agrees: the
+        status tensor (B, 8), the sensor features (``_sensor_inputs``), the start noise (None: ``torch.randn`` of
+        (B, *draw) on the CPU, where the reference draws it, transfuser_model_v2.py:593; ``"device"``: none, the
+        library draws it), int32 ``timesteps`` and the ``target`` trajectories. Returns ``(B, ins, out_device, nz, tt,
+        tg, keep)``: the dd_inputs descriptor with every pointer set, the device the caller's features live on, the
+        staged noise / timesteps / target (or None) and the staged tensors, which the caller holds until its call
+        is enqueued (the descriptor has only their addresses)."""
+        cam = features["camera_feature"]
+        out_device = cam.device if isinstance(cam, torch.Tensor) else torch.device("cpu")
+        st = self._dev(features["status_feature"])
+        B = st.shape[0]
+        cam, lid, ins = self._sensor_inputs(features, B)
+        if tuple(st.shape) != (B, 8):
+            raise ValueError(f"status_feature must be (B,8), got {tuple(st.shape)}")
+        if noise is None:
+            noise = torch.randn((B, *draw))
+        if isinstance(noise, str):
+            if noise != "device":
+                raise ValueError(f"noise must be a tensor, None or 'device', got {noise!r}")
+            nz = None
+        else:
+            nz = self._dev(noise)
+        tt = None if timesteps is None else self._dev(timesteps, dtype=torch.int32)
+        tg = None if target is None else self._dev(target)
+        # the graph reads the camera / LiDAR planes in place (through the handle's input table) and copies the rest
+        # on stream s: a caller that drops its tensors right after the call returns must not have their memory
+        # handed to other work while s still reads it (tensors allocated on another stream)
+        keep = [t for t in (cam, lid, st, nz, tt, tg) if t is not None]
+        for t in keep:
+            t.record_stream(s)
+        ins.status = st.data_ptr()
+        ins.noise = nz.data_ptr() if nz is not None else None
+        return B, ins, out_device, nz, tt, tg, keep
+
+    def _head_outputs(self, outs, res, B, dev):
+        """Allocate the BEV-semantic / agent head outputs into ``res`` and name them in the ctypes ``outs`` struct."""
+        cfg = self.config
+        res["bev_semantic_map"] = torch.empty(
+            (B, 7, cfg.lidar_resolution_height // 2, cfg.lidar_resolution_width), device=dev)
+        res["agent_states"] = torch.empty((B, cfg.num_bounding_boxes, 5), device=dev)
+        res["agent_labels"] = torch.empty((B, cfg.num_bounding_boxes), device=dev)
+        for k in ("bev_semantic_map", "agent_states", "agent_labels"):
+            setattr(outs, k, res[k].data_ptr())
+
+    @staticmethod
+    def _to_caller(res, out_device):
+        return res if out_device.type == "cuda" else {k: v.to(out_device) for k, v in res.items()}
+
+    def _run_checked(self, run, what, flagged=False):
+        """``run()`` with the numerics flags cleared; if a kernel raised one (or the caller saw it: ``flagged``), warn
+        and run again on the fp32-MFMA path. Raises if the fp32 run raises a flag as well."""
+        if not flagged:
+            self.numerics_flags(clear=True)
+            out = run()
+            if not self.numerics_flags(clear=True):
+                return out
+        mode = self.gemm_mode()
+        warnings.warn(f"ddmi: numerics flag raised in gemm mode {mode!r}; re-running {what} in fp32")
+        self.set_gemm_mode("fp32")
+        try:
+            out = run()
+        finally:
+            self.set_gemm_mode(mode)
+        if self.numerics_flags(clear=True):
+            raise _lib.DDMIError(f"numerics flag raised by the fp32 {what.split()[-1]} as well")
+        return out
+
     def forward(self, features: Dict[str, torch.Tensor], noise: Optional[torch.Tensor] = None,
                 steps: Optional[int] = None, heads: bool = False, modes: bool = False,
                 stream: Optional[torch.cuda.Stream] = None, safe: bool = False) -> Dict[str, torch.Tensor]:
@@ -187,25 +255,13 @@ class DiffusionDriveModel:
         if noise is None:
             B = torch.as_tensor(features["status_feature"]).shape[0]
             noise = torch.randn((B, self.config.num_modes, self.config.trajectory_sampling.num_poses, 2))
-        self.numerics_flags(clear=True)
-        out = self._forward(features, noise, steps, heads, modes, stream)
-        if self.numerics_flags(clear=True):
-            out = self.rerun_fp32(features, noise, steps, heads, modes, stream)
-        return out
+        return self._run_checked(lambda: self._forward(features, noise, steps, heads, modes, stream), "the forward")
 
     def rerun_fp32(self, features, noise, steps=None, heads=False, modes=False, stream=None):
         """Re-run a forward whose numerics flag was raised directly on the fp32-MFMA path (warns; raises if
         the fp32 forward raises a flag as well). ``noise`` must be the tensor the flagged forward used."""
-        mode = self.gemm_mode()
-        warnings.warn(f"ddmi: numerics flag raised in gemm mode {mode!r}; re-running the forward in fp32")
-        self.set_gemm_mode("fp32")
-        try:
-            out = self._forward(features, noise, steps, heads, modes, stream)
-        finally:
-            self.set_gemm_mode(mode)
-        if self.numerics_flags(clear=True):
-            raise _lib.DDMIError("numerics flag raised by the fp32 forward as well")
-        return out
+        return self._run_checked(lambda: self._forward(features, noise, steps, heads, modes, stream), "the forward",
+                                 flagged=True)
 
     def set_seed(self, seed: int, first_scene: int = 0):
         """Seed of the device noise draw (``noise="device"``); restarts its stream at global scene index
@@ -220,63 +276,28 @@ class DiffusionDriveModel:
     def _forward(self, features, noise, steps, heads, modes, stream) -> Dict[str, torch.Tensor]:
         # stage inputs and allocate outputs on the stream the forward is ordered after, so the caching
         # allocator ties their lifetime to it (the handle's stream waits on that stream and hands back to it)
+        cfg = self.config
+        Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
         dev = torch.device(f"cuda:{self.device}")
         s = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(s):
-            return self._forward_on(features, noise, steps, heads, modes, s)
-
-    def _forward_on(self, features, noise, steps, heads, modes, s) -> Dict[str, torch.Tensor]:
-        cfg = self.config
-        cam = features["camera_feature"]
-        out_device = cam.device if isinstance(cam, torch.Tensor) else torch.device("cpu")
-        st = self._dev(features["status_feature"])
-        B = st.shape[0]
-        Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
-        cam, lid, ins = self._sensor_inputs(features, B)
-        if tuple(st.shape) != (B, 8):
-            raise ValueError(f"status_feature must be (B,8), got {tuple(st.shape)}")
-        ins.status = st.data_ptr()
-        if noise is None:
-            # the reference draws its DDIM start noise here (transfuser_model_v2.py:593), on CPU
-            noise = torch.randn((B, Q, P, 2))
-        if isinstance(noise, str):
-            if noise != "device":
-                raise ValueError(f"noise must be a tensor, None or 'device', got {noise!r}")
-            nz = None
-        else:
-            nz = self._dev(noise)
-            if tuple(nz.shape) != (B, Q, P, 2):
+            B, ins, out_device, nz, _, _, keep = self._stage(features, s, noise, draw=(Q, P, 2))
+            if nz is not None and tuple(nz.shape) != (B, Q, P, 2):
                 raise ValueError(f"noise must be (B,{Q},{P},2), got {tuple(nz.shape)}")
-        # the graph reads the camera / LiDAR planes in place (through the handle's input table) and copies status /
-        # noise on stream s: a caller that drops its tensors right after forward() returns must not have their
-        # memory handed to other work while s still reads it (tensors allocated on another stream)
-        for t in (cam, lid, st, nz):
-            if t is not None:
-                t.record_stream(s)
-        dev = cam.device
-        traj = torch.empty((B, P, 3), device=dev)
-        outs = _lib.DDOutputs()
-        outs.trajectory = traj.data_ptr()
-        res = {"trajectory": traj}
-        if modes:
-            res["poses_reg"] = torch.empty((B, Q, P, 3), device=dev)
-            res["poses_cls"] = torch.empty((B, Q), device=dev)
-            outs.poses_reg = res["poses_reg"].data_ptr()
-            outs.poses_cls = res["poses_cls"].data_ptr()
-        if heads:
-            res["bev_semantic_map"] = torch.empty(
-                (B, 7, cfg.lidar_resolution_height // 2, cfg.lidar_resolution_width), device=dev)
-            res["agent_states"] = torch.empty((B, cfg.num_bounding_boxes, 5), device=dev)
-            res["agent_labels"] = torch.empty((B, cfg.num_bounding_boxes), device=dev)
-            outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
-            outs.agent_states = res["agent_states"].data_ptr()
-            outs.agent_labels = res["agent_labels"].data_ptr()
-        ins.noise = nz.data_ptr() if nz is not None else None
-        _lib.check(self.lib.dd_forward_in(self.handle, ctypes.byref(ins), B, int(steps or cfg.denoise_steps),
-                                          ctypes.byref(outs), s.cuda_stream), self.lib)
-        if out_device.type != "cuda":
-            res = {k: v.to(out_device) for k, v in res.items()}
-        return res
+            outs = _lib.DDOutputs()
+            res = {"trajectory": torch.empty((B, P, 3), device=dev)}
+            outs.trajectory = res["trajectory"].data_ptr()
+            if modes:
+                res["poses_reg"] = torch.empty((B, Q, P, 3), device=dev)
+                res["poses_cls"] = torch.empty((B, Q), device=dev)
+                outs.poses_reg = res["poses_reg"].data_ptr()
+                outs.poses_cls = res["poses_cls"].data_ptr()
+            if heads:
+                self._head_outputs(outs, res, B, dev)
+            _lib.check(self.lib.dd_forward_in(self.handle, ctypes.byref(ins), B, int(steps or cfg.denoise_steps),
+                                              ctypes.byref(outs), s.cuda_stream), self.lib)
+            del keep
+            return self._to_caller(res, out_device)
 
     __call__ = forward
 
@@ -305,58 +326,30 @@ class DiffusionDriveModel:
                 raise ValueError(f"noise must be a tensor, None or 'device', got {noise!r}")
         elif noise is not None and tuple(torch.as_tensor(noise).shape) != (B, S, Q, P, 2):
             raise ValueError(f"noise must be (B,{S},{Q},{P},2) with B = {B}, got {tuple(torch.as_tensor(noise).shape)}")
-        if noise is None:
-            noise = torch.randn((B, S, Q, P, 2))
         dev = torch.device(f"cuda:{self.device}")
         s = stream or torch.cuda.current_stream(dev)
         with torch.cuda.stream(s):
-            return self._forward_samples_on(features, S, noise, steps, heads, modes, best, s)
-
-    def _forward_samples_on(self, features, S, noise, steps, heads, modes, best, s) -> Dict[str, torch.Tensor]:
-        cfg = self.config
-        cam = features["camera_feature"]
-        out_device = cam.device if isinstance(cam, torch.Tensor) else torch.device("cpu")
-        st = self._dev(features["status_feature"])
-        B = st.shape[0]
-        Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
-        cam, lid, ins = self._sensor_inputs(features, B)
-        if tuple(st.shape) != (B, 8):
-            raise ValueError(f"status_feature must be (B,8), got {tuple(st.shape)}")
-        ins.status = st.data_ptr()
-        nz = None if isinstance(noise, str) else self._dev(noise)
-        # as _forward_on: the caller may drop its tensors while stream s still reads them
-        for t in (cam, lid, st, nz):
-            if t is not None:
-                t.record_stream(s)
-        dev = cam.device
-        outs = _lib.DDSampleOutputs()
-        res = {"trajectory": torch.empty((B, S, P, 3), device=dev)}
-        outs.trajectory = res["trajectory"].data_ptr()
-        if modes:
-            res["poses_reg"] = torch.empty((B, S, Q, P, 3), device=dev)
-            res["poses_cls"] = torch.empty((B, S, Q), device=dev)
-            outs.poses_reg = res["poses_reg"].data_ptr()
-            outs.poses_cls = res["poses_cls"].data_ptr()
-        if best:
-            res["best_trajectory"] = torch.empty((B, P, 3), device=dev)
-            res["best_index"] = torch.empty((B,), device=dev, dtype=torch.int32)
-            outs.best_trajectory = res["best_trajectory"].data_ptr()
-            outs.best_index = res["best_index"].data_ptr()
-        if heads:
-            res["bev_semantic_map"] = torch.empty(
-                (B, 7, cfg.lidar_resolution_height // 2, cfg.lidar_resolution_width), device=dev)
-            res["agent_states"] = torch.empty((B, cfg.num_bounding_boxes, 5), device=dev)
-            res["agent_labels"] = torch.empty((B, cfg.num_bounding_boxes), device=dev)
-            outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
-            outs.agent_states = res["agent_states"].data_ptr()
-            outs.agent_labels = res["agent_labels"].data_ptr()
-        ins.noise = nz.data_ptr() if nz is not None else None
-        _lib.check(self.lib.dd_forward_samples_in(self.handle, ctypes.byref(ins), B, S,
-                                                  int(steps or cfg.denoise_steps), ctypes.byref(outs), s.cuda_stream),
-                   self.lib)
-        if out_device.type != "cuda":
-            res = {k: v.to(out_device) for k, v in res.items()}
-        return res
+            B, ins, out_device, _, _, _, keep = self._stage(features, s, noise, draw=(S, Q, P, 2))
+            outs = _lib.DDSampleOutputs()
+            res = {"trajectory": torch.empty((B, S, P, 3), device=dev)}
+            outs.trajectory = res["trajectory"].data_ptr()
+            if modes:
+                res["poses_reg"] = torch.empty((B, S, Q, P, 3), device=dev)
+                res["poses_cls"] = torch.empty((B, S, Q), device=dev)
+                outs.poses_reg = res["poses_reg"].data_ptr()
+                outs.poses_cls = res["poses_cls"].data_ptr()
+            if best:
+                res["best_trajectory"] = torch.empty((B, P, 3), device=dev)
+                res["best_index"] = torch.empty((B,), device=dev, dtype=torch.int32)
+                outs.best_trajectory = res["best_trajectory"].data_ptr()
+                outs.best_index = res["best_index"].data_ptr()
+            if heads:
+                self._head_outputs(outs, res, B, dev)
+            _lib.check(self.lib.dd_forward_samples_in(self.handle, ctypes.byref(ins), B, S,
+                                                      int(steps or cfg.denoise_steps), ctypes.byref(outs),
+                                                      s.cuda_stream), self.lib)
+            del keep
+            return self._to_caller(res, out_device)
 
     def forward_train(self, features: Dict[str, torch.Tensor], targets: Optional[Dict[str, torch.Tensor]] = None,
                       timesteps: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
@@ -388,42 +381,22 @@ class DiffusionDriveModel:
             raise ValueError(f"timesteps must lie in [0, {cfg.num_train_timesteps})")
         if not safe:
             return self._forward_train(features, targets, timesteps, noise, heads, stream)
-        self.numerics_flags(clear=True)
-        res = self._forward_train(features, targets, timesteps, noise, heads, stream)
-        if self.numerics_flags(clear=True):
-            mode = self.gemm_mode()
-            warnings.warn(f"ddmi: numerics flag raised in gemm mode {mode!r}; re-running forward_train in fp32")
-            self.set_gemm_mode("fp32")
-            try:
-                res = self._forward_train(features, targets, timesteps, noise, heads, stream)
-            finally:
-                self.set_gemm_mode(mode)
-            if self.numerics_flags(clear=True):
-                raise _lib.DDMIError("numerics flag raised by the fp32 forward_train as well")
-        return res
+        return self._run_checked(lambda: self._forward_train(features, targets, timesteps, noise, heads, stream),
+                                 "forward_train")
 
     def _forward_train(self, features, targets, timesteps, noise, heads, stream) -> Dict[str, torch.Tensor]:
         cfg = self.config
         dev = torch.device(f"cuda:{self.device}")
         cur = torch.cuda.current_stream(dev)
         s = stream or cur
-        B = torch.as_tensor(features["status_feature"]).shape[0]
         Q, P = cfg.num_modes, cfg.trajectory_sampling.num_poses
         with torch.cuda.stream(s):
-            cam, lid, ins = self._sensor_inputs(features, B)
-            st = self._dev(features["status_feature"])
-            nz = self._dev(noise)
-            tt = self._dev(timesteps, dtype=torch.int32)
+            B, ins, _, nz, tt, tg, keep = self._stage(features, s, noise, timesteps=timesteps,
+                                                      target=(targets or {}).get("trajectory"))
             if tuple(nz.shape) != (B, Q, P, 2) or tuple(tt.shape) != (B,):
                 raise ValueError(f"noise must be (B,{Q},{P},2) and timesteps (B,), got {tuple(nz.shape)}, {tuple(tt.shape)}")
-            tg = None
-            if targets is not None and targets.get("trajectory") is not None:
-                tg = self._dev(targets["trajectory"])
-                if tuple(tg.shape) != (B, P, 3):
-                    raise ValueError(f"targets['trajectory'] must be (B,{P},3), got {tuple(tg.shape)}")
-            for t in (cam, lid, st, nz, tt, tg):
-                if t is not None:
-                    t.record_stream(s)
+            if tg is not None and tuple(tg.shape) != (B, P, 3):
+                raise ValueError(f"targets['trajectory'] must be (B,{P},3), got {tuple(tg.shape)}")
             res = {"trajectory": torch.empty((B, P, 3), device=dev),
                    "poses_reg_list": [torch.empty((B, Q, P, 3), device=dev) for _ in range(2)],
                    "poses_cls_list": [torch.empty((B, Q), device=dev) for _ in range(2)]}
@@ -437,18 +410,12 @@ class DiffusionDriveModel:
                 loss = torch.empty(3, device=dev)
                 outs.loss = loss.data_ptr()
             if heads:
-                res["bev_semantic_map"] = torch.empty((B, 7, cfg.lidar_resolution_height // 2,
-                                                       cfg.lidar_resolution_width), device=dev)
-                res["agent_states"] = torch.empty((B, cfg.num_bounding_boxes, 5), device=dev)
-                res["agent_labels"] = torch.empty((B, cfg.num_bounding_boxes), device=dev)
-                outs.bev_semantic_map = res["bev_semantic_map"].data_ptr()
-                outs.agent_states = res["agent_states"].data_ptr()
-                outs.agent_labels = res["agent_labels"].data_ptr()
-            ins.status, ins.noise = st.data_ptr(), nz.data_ptr()
+                self._head_outputs(outs, res, B, dev)
             _lib.check(self.lib.dd_forward_train_in(self.handle, ctypes.byref(ins), tt.data_ptr(),
                                                     tg.data_ptr() if tg is not None else None, B,
                                                     float(cfg.trajectory_cls_weight), float(cfg.trajectory_reg_weight),
                                                     ctypes.byref(outs), s.cuda_stream), self.lib)
+            del keep
         if s != cur:
             # the outputs (the loss reduction last) were written on s: order the caller's stream after it, so a
             # .cpu() / .item() on the current stream reads finished values

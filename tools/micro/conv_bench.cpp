@@ -149,12 +149,13 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
+    ConvRoute route;  // of the last timed launch
     auto timed = [&](const ConvArgs& c) {
       for (int i = 0; i < 3; ++i) launch_conv_gemm(c, st);
       std::vector<float> ts;
       for (int i = 0; i < reps; ++i) {
         CK(hipEventRecord(e0, st));
-        launch_conv_gemm(c, st);
+        route = launch_conv_gemm(c, st);
         CK(hipEventRecord(e1, st));
         CK(hipEventSynchronize(e1));
         float ms;
@@ -187,7 +188,7 @@ int main(int argc, char** argv) {
       const int NWG = 8192;  // g_x6_st
 #endif
       std::vector<unsigned long long> t(NWG * 4);
-      if (rd(t.data(), NWG * 4) == 0 && std::string(last_conv_kernel()) == kname) {
+      if (rd(t.data(), NWG * 4) == 0 && std::string(route.kernel) == kname) {
         int n = 0;
         double pro = 0, mainl = 0, epi = 0;
         for (int w = 0; w < NWG; ++w) {
