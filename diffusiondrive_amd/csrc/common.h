@@ -38,6 +38,20 @@ struct View4 {
   float* p = nullptr;
   int64_t sn = 0, sh = 0, sw = 0, sc = 1;
 };
+// The layouts the forward uses (a read-only operand is viewed through the same type).
+// Rows of W pixels x C channels, the images sn apart (sn = 0: one image for every n)
+inline View4 hwc(const float* p, int64_t sn, int W, int C) {
+  return {const_cast<float*>(p), sn, (int64_t)W * C, C, 1};
+}
+// Contiguous NHWC map
+inline View4 nhwc(const float* p, int H, int W, int C) { return hwc(p, (int64_t)H * W * C, W, C); }
+// Channels c0.. of a map: the pointer moves, the strides stay the full map's
+inline View4 channels_from(View4 v, int64_t c0) {
+  v.p += c0 * v.sc;
+  return v;
+}
+// Grouped rows: row r of group g at p + g * gs + r * rs (dense rows are the one-group case)
+inline View4 row_view(const float* p, int64_t gs, int64_t rs) { return {const_cast<float*>(p), gs, rs, 0, 1}; }
 
 // ----------------------------------------------------------------------------------------
 // Implicit-GEMM convolution / GEMM on fp32 MFMA (conv_gemm.hip).
@@ -116,6 +130,88 @@ struct ConvArgs {
   // subset's rows get the K walk and epilogue of the full launch by construction, whatever the batch.
   int64_t route_rows = 0;
 };
+// Host-side builders: every launch describes its operands as views and takes its ConvArgs from here. The caller
+// attaches the weight (wgt / bias, the split images) and whatever scratch the launch may use.
+struct ConvGeom {
+  int KH = 1, KW = 1, stride = 1, pad = 0, Cout = 0;
+};
+// Convolution of the (N, H, W, Cin) map `in` into `out`, plus the optional residual `res` (both indexed by the
+// output pixel). ldb is the dense K of the geometry.
+inline ConvArgs conv_args(View4 in, int N, int H, int W, int Cin, ConvGeom g, View4 out, int relu = 0,
+                          View4 res = {}) {
+  ConvArgs a;
+  a.in = in.p;
+  a.in_sn = in.sn;
+  a.in_sh = in.sh;
+  a.in_sw = in.sw;
+  a.H = H;
+  a.W = W;
+  a.Cin = Cin;
+  a.ldb = (int64_t)g.KH * g.KW * Cin;
+  a.res = res.p;
+  a.res_sn = res.sn;
+  a.res_sh = res.sh;
+  a.res_sw = res.sw;
+  a.out = out.p;
+  a.out_sn = out.sn;
+  a.out_sh = out.sh;
+  a.out_sw = out.sw;
+  a.Nimg = N;
+  a.Ho = (H + 2 * g.pad - g.KH) / g.stride + 1;
+  a.Wo = (W + 2 * g.pad - g.KW) / g.stride + 1;
+  a.Cout = g.Cout;
+  a.KH = g.KH;
+  a.KW = g.KW;
+  a.stride = g.stride;
+  a.pad = g.pad;
+  a.relu = relu;
+  return a;
+}
+// C = A W^T over G groups of R rows of K floats, N outputs per row (A, C, res: row_view()): the 1 x 1 conv with
+// Nimg = G, H = Ho = R, W = Wo = 1.
+inline ConvArgs gemm_args(View4 A, int G, int R, int K, int N, View4 C, int relu = 0, View4 res = {}) {
+  return conv_args(A, G, R, 1, K, ConvGeom{1, 1, 1, 0, N}, C, relu, res);
+}
+// K slice [k0, k0 + a.Cin) of a weight whose rows are ldb floats: the attached weight pointers move, the row
+// strides stay (the fp16 images share the K order; 16-B aligned slices only).
+inline void slice_k(ConvArgs& a, int k0, int64_t ldb) {
+  a.wgt += k0;
+  a.ldb = ldb;
+  if (a.wh) a.wh += k0;
+  if (a.wl) a.wl += k0;
+}
+// Fused LayerNorm of the output rows into y (ConvArgs::ln_out)
+inline void fold_ln(ConvArgs& a, float* y, const float* g, const float* b) {
+  a.ln_out = y;
+  a.ln_g = g;
+  a.ln_b = b;
+}
+// Fused p x p mean pooling of the output into `out` (+ add, broadcast over n; ConvArgs::pool_out)
+inline void pool_into(ConvArgs& a, int p, View4 out, View4 add) {
+  a.pool_out = out.p;
+  a.pool_p = p;
+  a.pool_sn = out.sn;
+  a.pool_sh = out.sh;
+  a.pool_sw = out.sw;
+  a.pool_add = add.p;
+  a.pool_add_sh = add.sh;
+  a.pool_add_sw = add.sw;
+}
+// The gathered-rows form (ConvArgs::rowmap) of a stride-1 conv over a.Nimg images: MR output rows, row m at
+// a.out + m * a.out_sh. counts (optional): the compacted form, `groups` row groups of MR / groups slots.
+inline ConvArgs gathered_rows(ConvArgs a, const int* rowmap, int MR, int groups = 0, const int* counts = nullptr) {
+  a.rowmap = rowmap;
+  a.rowmap_nimg = a.Nimg;
+  a.rowmap_groups = groups;
+  if (counts) {
+    a.rowcount = counts;
+    a.rowcap = MR / groups;
+  }
+  a.Nimg = 1;
+  a.Ho = MR;
+  a.Wo = 1;
+  return a;
+}
 constexpr unsigned DD_NUM_F16_OVERFLOW = 1u;  // an activation |x| >= 65504 met the f16x3 split
 constexpr unsigned DD_NUM_SYNC_TIMEOUT = 2u;  // a megakernel's inter-workgroup wait gave up (tfdec_mk groups)
 // a megakernel's inter-workgroup counter held a value no healthy launch leaves there (an arrival saw more or fewer

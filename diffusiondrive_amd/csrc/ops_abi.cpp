@@ -126,38 +126,31 @@ int dd_op_bevproj(const float* p3, int64_t p3_ld, const float* kvp, const float*
   });
 }
 
+// the contiguous NHWC conv of dd_op_conv2d / dd_op_conv2d_x3 (the residual in the output's layout)
+static ConvArgs conv2d_args(const float* in, int B, int H, int W, int Cin, const float* wgt, const float* bias,
+                            const float* res, float* out, int Cout, int KH, int KW, int stride, int pad, int relu) {
+  const int Ho = (H + 2 * pad - KH) / stride + 1, Wo = (W + 2 * pad - KW) / stride + 1;
+  ConvArgs a = conv_args(nhwc(in, H, W, Cin), B, H, W, Cin, ConvGeom{KH, KW, stride, pad, Cout},
+                         nhwc(out, Ho, Wo, Cout), relu, nhwc(res, Ho, Wo, Cout));
+  a.wgt = wgt;
+  a.bias = bias;
+  return a;
+}
+// the split images of `x` (uploaded in `ar`) for prec 0 (f16x3) / 1 (bf16)
+static void attach_split(ConvArgs& a, const Arena& ar, const SplitW& x, int prec, unsigned* flags) {
+  a.prec = prec;
+  a.wh = reinterpret_cast<const uint16_t*>(ar.ptr(prec ? x.b16 : x.hi));
+  a.wl = reinterpret_cast<const uint16_t*>(ar.ptr(x.lo));
+  a.wsinv = ar.ptr(x.sinv);
+  a.ldh = x.ldh;
+  a.flags = flags;
+}
+
 int dd_op_conv2d(const float* in, int B, int H, int W, int Cin, const float* wgt, const float* bias, const float* res,
                  float* out, int Cout, int KH, int KW, int stride, int pad, int relu, void* stream) {
   return op_guard([&] {
-    ConvArgs a;
-    a.in = in;
-    a.in_sw = Cin;
-    a.in_sh = (int64_t)W * Cin;
-    a.in_sn = (int64_t)H * W * Cin;
-    a.H = H;
-    a.W = W;
-    a.Cin = Cin;
-    a.wgt = wgt;
-    a.ldb = (int64_t)KH * KW * Cin;
-    a.bias = bias;
-    a.Nimg = B;
-    a.Ho = (H + 2 * pad - KH) / stride + 1;
-    a.Wo = (W + 2 * pad - KW) / stride + 1;
-    a.Cout = Cout;
-    a.out = out;
-    a.out_sw = Cout;
-    a.out_sh = (int64_t)a.Wo * Cout;
-    a.out_sn = (int64_t)a.Ho * a.Wo * Cout;
-    a.res = res;
-    a.res_sw = a.out_sw;
-    a.res_sh = a.out_sh;
-    a.res_sn = a.out_sn;
-    a.KH = KH;
-    a.KW = KW;
-    a.stride = stride;
-    a.pad = pad;
-    a.relu = relu;
-    ran(launch_conv_gemm(a, S(stream)));
+    ran(launch_conv_gemm(conv2d_args(in, B, H, W, Cin, wgt, bias, res, out, Cout, KH, KW, stride, pad, relu),
+                         S(stream)));
   });
 }
 
@@ -173,42 +166,10 @@ int dd_op_conv2d_x3(const float* in, int B, int H, int W, int Cin, const float* 
     Arena ar;
     const SplitW x = prep_split(ar, hw.data(), Cout, K);
     ar.upload();
-    ConvArgs a;
-    a.in = in;
-    a.in_sw = Cin;
-    a.in_sh = (int64_t)W * Cin;
-    a.in_sn = (int64_t)H * W * Cin;
-    a.H = H;
-    a.W = W;
-    a.Cin = Cin;
-    a.wgt = wgt;
-    a.ldb = K;
-    a.bias = bias;
-    a.Nimg = B;
-    a.Ho = (H + 2 * pad - KH) / stride + 1;
-    a.Wo = (W + 2 * pad - KW) / stride + 1;
-    a.Cout = Cout;
-    a.out = out;
-    a.out_sw = Cout;
-    a.out_sh = (int64_t)a.Wo * Cout;
-    a.out_sn = (int64_t)a.Ho * a.Wo * Cout;
-    a.res = res;
-    a.res_sw = a.out_sw;
-    a.res_sh = a.out_sh;
-    a.res_sn = a.out_sn;
-    a.KH = KH;
-    a.KW = KW;
-    a.stride = stride;
-    a.pad = pad;
-    a.relu = relu;
+    ConvArgs a = conv2d_args(in, B, H, W, Cin, wgt, bias, res, out, Cout, KH, KW, stride, pad, relu);
     if (prec != 0 && prec != 1) throw std::invalid_argument("prec must be 0 (f16x3) or 1 (bf16)");
-    a.prec = prec;
-    a.wh = reinterpret_cast<const uint16_t*>(ar.ptr(prec ? x.b16 : x.hi));
-    a.wl = reinterpret_cast<const uint16_t*>(ar.ptr(x.lo));
-    a.wsinv = ar.ptr(x.sinv);
-    a.ldh = x.ldh;
-    a.flags = flags;
-    // K-split scratch, as the forward provides it (runtime.cpp: conv): small grids may take conv_x3's split form
+    attach_split(a, ar, x, prec, flags);
+    // K-split scratch, as the forward provides it (runtime.cpp: run): small grids may take conv_x3's split form
     const int64_t mo = (int64_t)B * a.Ho * a.Wo * Cout;
     float* part = nullptr;
     if (prec == 0 && mo <= (1 << 20)) {
@@ -264,31 +225,12 @@ static int dd_op_stem_pool_impl(const void* in, int src_c, int B, int H, int W, 
     Arena ar;
     const SplitW x = prep_split(ar, hw.data(), Cout, K);
     ar.upload();
-    ConvArgs a;
-    a.in = u8 ? nullptr : static_cast<const float*>(in);
-    a.in_sw = Cin;
-    a.in_sh = (int64_t)W * Cin;
-    a.in_sn = (int64_t)H * W * Cin;
-    a.H = H;
-    a.W = W;
-    a.Cin = Cin;
+    // the kernel writes only the pooled map: no stem output view
+    ConvArgs a = conv_args(nhwc(u8 ? nullptr : static_cast<const float*>(in), H, W, Cin), B, H, W, Cin,
+                           ConvGeom{7, 7, 2, 3, Cout}, View4{}, true);
     a.wgt = wgt;
-    a.ldb = K;
     a.bias = bias;
-    a.Nimg = B;
-    a.Ho = (H + 6 - 7) / 2 + 1;
-    a.Wo = (W + 6 - 7) / 2 + 1;
-    a.Cout = Cout;
-    a.KH = a.KW = 7;
-    a.stride = 2;
-    a.pad = 3;
-    a.relu = 1;
-    a.prec = prec;
-    a.wh = reinterpret_cast<const uint16_t*>(ar.ptr(prec ? x.b16 : x.hi));
-    a.wl = reinterpret_cast<const uint16_t*>(ar.ptr(x.lo));
-    a.wsinv = ar.ptr(x.sinv);
-    a.ldh = x.ldh;
-    a.flags = flags;
+    attach_split(a, ar, x, prec, flags);
     const int hp = (a.Ho + 2 - 3) / 2 + 1, wp = (a.Wo + 2 - 3) / 2 + 1;
     // NCHW input of src_c channels: the kernel reads its address from a device word
     const void** word = nullptr;
@@ -350,20 +292,10 @@ int dd_build_lidar_u8(const float* xyz, const int64_t* offsets, int B, int chann
 int dd_op_gemm(const float* A, int M, int K, const float* W, const float* bias, const float* res, float* C, int N,
                int relu, void* stream) {
   return op_guard([&] {
-    ConvArgs a;
-    a.in = A;
-    a.in_sn = K;
-    a.Cin = K;
+    // M groups of one row each
+    ConvArgs a = gemm_args(row_view(A, K, K), M, 1, K, N, row_view(C, N, N), relu, row_view(res, N, N));
     a.wgt = W;
-    a.ldb = K;
     a.bias = bias;
-    a.res = res;
-    a.res_sn = N;
-    a.out = C;
-    a.out_sn = N;
-    a.Nimg = M;
-    a.Cout = N;
-    a.relu = relu;
     ran(launch_conv_gemm(a, S(stream)));
   });
 }
@@ -371,17 +303,10 @@ int dd_op_gemm(const float* A, int M, int K, const float* W, const float* bias, 
 int dd_op_gemm_batched(const float* A, const float* Bm, float* C, int batch, int M, int N, int K, int kn,
                        void* stream) {
   return op_guard([&] {
-    ConvArgs a;
-    a.in = A;
-    a.in_sn = K;
-    a.Cin = K;
+    ConvArgs a = gemm_args(row_view(A, K, K), M, 1, K, N, row_view(C, N, N));
     a.wgt = Bm;
     a.ldb = kn ? N : K;
     a.b_kn = kn;
-    a.out = C;
-    a.out_sn = N;
-    a.Nimg = M;
-    a.Cout = N;
     a.batch = batch;
     a.zdiv = 1;
     a.in_z1 = (int64_t)M * K;

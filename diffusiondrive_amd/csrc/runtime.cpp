@@ -784,6 +784,14 @@ class Model {
     return L;
   }
 
+  // value_proj + ReLU over the nimg images of `cross` at the MR gathered pixels `rows`, compact rows into vrows
+  // (groups / counts: gathered_rows)
+  ConvArgs value_rows_args(const Conv& vc, const float* cross, int nimg, int HB, int WB, const int* rows, int MR,
+                           float* vrows, int groups = 0, const int* counts = nullptr) {
+    const ConvArgs a = conv_args(nhwc(cross, HB, WB, vc.cin), nimg, HB, WB, vc.cin, geom(vc),
+                                 row_view(vrows, (int64_t)MR * vc.cout, vc.cout), true);
+    return gathered_rows(attach(a, vc.w, vc.b, vc.x3), rows, MR, groups, counts);
+  }
   // value_proj (3x3 conv 256 -> 256 + ReLU, blocks.py:68-76,114) of layer l evaluated only at the map
   // pixels the (step, layer)'s taps read: conv_x3 over the deduplicated row list `rows`
   // counts (nullable): the scenes' live-row counts - the launch then runs the scenes' rows compacted (full
@@ -795,20 +803,9 @@ class Model {
   void gathered_value(int l, const int* rows, const int* counts, float* vrows, const float* cross, int B, int nimg,
                       int HB, int WB, int MR, int busy_cus = 0) {
     const int d = 256;
-    ConvArgs a = conv_args(dl[l].vproj, cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, nimg, HB, WB, vrows,
-                           (int64_t)MR * d, d, 0, true, nullptr, 0, 0, 0);
-    a.Nimg = 1;
-    a.Ho = MR;
-    a.Wo = 1;
-    a.rowmap = rows;
-    a.rowmap_nimg = nimg;
-    a.rowmap_groups = B;
-    if (counts) {
-      a.rowcount = counts;
-      a.rowcap = MR / B;
-    }
-    const double fl = 2.0 * MR * (double)d * 9 * dl[l].vproj.cin_real;
     const Conv& vc = dl[l].vproj;
+    const ConvArgs a = value_rows_args(vc, cross, nimg, HB, WB, rows, MR, vrows, B, counts);
+    const double fl = 2.0 * MR * (double)d * 9 * vc.cin_real;
     if (value_splitk && counts && vproj_supported(vc.cin, vc.cout, HB, WB) && a.wh && a.prec == 0) {
       // value_proj.hip: compacted rows in 256-row tiles, two 128-channel halves each
       VprojArgs v;
@@ -853,7 +850,7 @@ class Model {
       ClassScope(const char*& cc, const char* v) : c(cc) { c = v; }
       ~ClassScope() { c = nullptr; }
     } cls(force_class, "value_proj");
-    launch("conv_x3", fl, [&] { return launch_conv_gemm(a, st); }, &a, -1.0, "form=conv_x3");
+    run(a, fl, false, "form=conv_x3");
   }
 
   // TrajectoryHead.forward_test (:578-641) as 1 + 2 x steps x 2 launches: the DDIM start + first taps, then
@@ -1239,88 +1236,52 @@ class Model {
     if (log) fclose(log);
   }
 
-  // route a conv / linear to the f16x3 split-MFMA kernel when that mode is on
-  void use_split(ConvArgs& a, const SplitW& x) {
-    if (gemm_mode == DD_GEMM_FP32 || x.hi == kNone) return;
+  // the weight of a launch: the fp32 image and bias, and the split images when the mode routes to them
+  ConvArgs attach(ConvArgs a, size_t w, size_t b, const SplitW& x) {
+    a.wgt = W(w);
+    a.bias = W(b);
+    if (gemm_mode == DD_GEMM_FP32 || x.hi == kNone) return a;
     a.prec = gemm_mode == DD_GEMM_BF16 ? 1 : 0;
     a.wh = reinterpret_cast<const uint16_t*>(W(a.prec ? x.b16 : x.hi));
     a.wl = reinterpret_cast<const uint16_t*>(W(x.lo));
     a.wsinv = W(x.sinv);
     a.ldh = x.ldh;
     a.flags = num_flags;
-  }
-
-  // GPT token pooling fused into the next conv's epilogue (conv_x6; see ConvArgs::pool_out): set before
-  // the conv, consumed by it; pool_done tells whether that conv wrote the tokens (otherwise the caller runs
-  // launch_avgpool, e.g. in the fp32 mode or when the conv routes elsewhere)
-  struct PoolSpec {
-    float* out = nullptr;
-    int64_t sn = 0, sh = 0, sw = 0;
-    const float* add = nullptr;
-    int64_t add_sh = 0, add_sw = 0;
-    int oh = 0, ow = 0;  // pooled grid
-  };
-  PoolSpec pool_next;
-  int pool_next_p = 0;
-  bool pool_done = false;
-
-  // conv on strided NHWC views
-  ConvArgs conv_args(const Conv& c, const float* in, int64_t isn, int64_t ish, int64_t isw, int N, int H, int Wd,
-                     float* out, int64_t osn, int64_t osh, int64_t osw, bool relu, const float* res, int64_t rsn,
-                     int64_t rsh, int64_t rsw) {
-    ConvArgs a;
-    a.in = in;
-    a.in_sn = isn;
-    a.in_sh = ish;
-    a.in_sw = isw;
-    a.H = H;
-    a.W = Wd;
-    a.Cin = c.cin;
-    a.wgt = W(c.w);
-    a.ldb = (int64_t)c.k * c.k * c.cin;
-    a.bias = W(c.b);
-    a.res = res;
-    a.res_sn = rsn;
-    a.res_sh = rsh;
-    a.res_sw = rsw;
-    a.out = out;
-    a.out_sn = osn;
-    a.out_sh = osh;
-    a.out_sw = osw;
-    a.Nimg = N;
-    a.Ho = (H + 2 * c.pad - c.k) / c.stride + 1;
-    a.Wo = (Wd + 2 * c.pad - c.k) / c.stride + 1;
-    a.Cout = c.cout;
-    a.KH = a.KW = c.k;
-    a.stride = c.stride;
-    a.pad = c.pad;
-    a.relu = relu;
-    use_split(a, c.x3);
-    if (pool_next_p > 0) {
-      a.pool_out = pool_next.out;
-      a.pool_p = pool_next_p;
-      a.pool_sn = pool_next.sn;
-      a.pool_sh = pool_next.sh;
-      a.pool_sw = pool_next.sw;
-      a.pool_add = pool_next.add;
-      a.pool_add_sh = pool_next.add_sh;
-      a.pool_add_sw = pool_next.add_sw;
-      pool_next_p = 0;
-    }
     return a;
   }
-  void conv(const Conv& c, const float* in, int64_t isn, int64_t ish, int64_t isw, int N, int H, int Wd, float* out,
-            int64_t osn, int64_t osh, int64_t osw, bool relu, const float* res = nullptr, int64_t rsn = 0,
-            int64_t rsh = 0, int64_t rsw = 0) {
-    ConvArgs a = conv_args(c, in, isn, ish, isw, N, H, Wd, out, osn, osh, osw, relu, res, rsn, rsh, rsw);
-    const double fl = 2.0 * N * a.Ho * a.Wo * (double)c.cout * c.k * c.k * c.cin_real;
-    // small outputs (batch-1-sized maps): K-split scratch for conv_x3, one per stream of the forward
-    const int64_t mo = (int64_t)N * a.Ho * a.Wo * c.cout;
-    if (a.wh && a.prec == 0 && mo <= (int64_t(1) << 20)) {
+  // The tail of every conv / GEMM launch (a: built by common.h's builders, weight attached).
+  // splitk: small outputs (batch-1-sized maps) get the K-split scratch for conv_x3, one per stream of the forward
+  ConvRoute run(ConvArgs a, double fl, bool splitk = false, const char* note = nullptr) {
+    const int64_t mo = (int64_t)a.Nimg * a.Ho * a.Wo * a.Cout;
+    if (splitk && a.wh && a.prec == 0 && mo <= (int64_t(1) << 20)) {
       a.split_cap = 8 * mo;
       a.split_part = buf(in_side ? "x3_split_side" : "x3_split_main", (size_t)a.split_cap);
     }
-    pool_done = launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a).pooled;
+    return launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a, -1.0, note);
+  }
+
+  // GPT token pooling fused into a conv's epilogue (conv_x6; see ConvArgs::pool_out): the oh x ow token grid `out`
+  // (+ add). The conv's route tells whether it wrote the tokens (otherwise the caller runs launch_avgpool, e.g. in
+  // the fp32 mode or when the conv routes elsewhere)
+  struct PoolSpec {
+    View4 out, add;
+    int oh = 0, ow = 0;
+  };
+
+  static ConvGeom geom(const Conv& c) { return {c.k, c.k, c.stride, c.pad, c.cout}; }
+  // conv on strided NHWC views; pool: also fused into it when its square windows tile the output exactly
+  ConvRoute conv(const Conv& c, View4 in, int N, int H, int Wd, View4 out, bool relu, View4 res = {},
+                 const PoolSpec* pool = nullptr) {
+    ConvArgs a = attach(conv_args(in, N, H, Wd, c.cin, geom(c), out, relu, res), c.w, c.b, c.x3);
+    if (pool && a.Ho % pool->oh == 0 && a.Wo % pool->ow == 0 && a.Ho / pool->oh == a.Wo / pool->ow)
+      pool_into(a, a.Ho / pool->oh, pool->out, pool->add);
+    return run(a, 2.0 * N * a.Ho * a.Wo * (double)c.cout * c.k * c.k * c.cin_real, true);
+  }
+  // contiguous NHWC conv (the residual, if any, in the output's layout)
+  ConvRoute conv_c(const Conv& c, const float* in, int N, int H, int Wd, float* out, bool relu,
+                   const float* res = nullptr, const PoolSpec* pool = nullptr) {
+    const int Ho = (H + 2 * c.pad - c.k) / c.stride + 1, Wo = (Wd + 2 * c.pad - c.k) / c.stride + 1;
+    return conv(c, nhwc(in, H, Wd, c.cin), N, H, Wd, nhwc(out, Ho, Wo, c.cout), relu, nhwc(res, Ho, Wo, c.cout), pool);
   }
   // timm stem conv1 / bn1 / act1 + maxpool 3x3/2: one fused kernel (stem_pool.hip) in f16x3 mode,
   // otherwise the conv into `stem` and the pool from it
@@ -1330,8 +1291,8 @@ class Model {
   void stem_and_pool(const Conv& c, const float* in4, int N, int H, int Wd, float* stem, float* pool, int hp, int wp,
                      int in_idx, int in_c, int in_u8 = 0, const float* lut = nullptr) {
     const int hs = (H + 2 * c.pad - c.k) / c.stride + 1, ws = (Wd + 2 * c.pad - c.k) / c.stride + 1;
-    ConvArgs a = conv_args(c, in4, (int64_t)H * Wd * c.cin, (int64_t)Wd * c.cin, c.cin, N, H, Wd, stem,
-                           (int64_t)hs * ws * c.cout, (int64_t)ws * c.cout, c.cout, true, nullptr, 0, 0, 0);
+    const ConvArgs a = attach(
+        conv_args(nhwc(in4, H, Wd, c.cin), N, H, Wd, c.cin, geom(c), nhwc(stem, hs, ws, c.cout), true), c.w, c.b, c.x3);
     const double fl = 2.0 * N * hs * ws * (double)c.cout * c.k * c.k * c.cin_real;
     const bool nchw = use_nchw_stem();
     // byte model: the input once at its element size (the NHWC4 copy has 4 floats per pixel, the NCHW tensor in_c;
@@ -1348,125 +1309,37 @@ class Model {
     conv_c(c, in4, N, H, Wd, stem, true);
     launch("pool", 0, [&] { launch_maxpool3x3s2(stem, pool, N, hs, ws, c.cout, hp, wp, st); });
   }
-  // contiguous NHWC conv; returns output spatial size
-  void conv_c(const Conv& c, const float* in, int N, int H, int Wd, float* out, bool relu, const float* res = nullptr) {
-    const int Ho = (H + 2 * c.pad - c.k) / c.stride + 1, Wo = (Wd + 2 * c.pad - c.k) / c.stride + 1;
-    conv(c, in, (int64_t)H * Wd * c.cin, (int64_t)Wd * c.cin, c.cin, N, H, Wd, out, (int64_t)Ho * Wo * c.cout,
-         (int64_t)Wo * c.cout, c.cout, relu, res, (int64_t)Ho * Wo * c.cout, (int64_t)Wo * c.cout, c.cout);
-  }
 
-  // C[M][N] = A[M][K] W^T (+bias) (+res) (relu); rows grouped: row m -> (m / G, m % G) with
-  // A offset (m/G)*a_gs + (m%G)*a_rs (dense when G == M).
-  void gemm(const Lin& L, const float* A, int64_t lda, int M, float* C, int64_t ldc, bool relu = false,
-            const float* res = nullptr, int64_t ldr = 0) {
-    gemm_g(L, A, (int64_t)M * lda, lda, 1, M, C, (int64_t)M * ldc, ldc, relu, res, (int64_t)M * ldr, ldr);
-  }
+  // C = A W^T (+bias) (+res) (relu) over G groups of R rows (A, C, res: row_view())
   // route_rows: see ConvArgs::route_rows (a row subset of another GEMM takes that GEMM's tile form)
-  void gemm_g(const Lin& L, const float* A, int64_t a_gs, int64_t a_rs, int G, int R, float* C, int64_t c_gs,
-              int64_t c_rs, bool relu = false, const float* res = nullptr, int64_t r_gs = 0, int64_t r_rs = 0,
-              int64_t route_rows = 0) {
-    ConvArgs a;
+  void gemm_g(const Lin& L, View4 A, int G, int R, View4 C, bool relu = false, View4 res = {}, int64_t route_rows = 0) {
+    ConvArgs a = attach(gemm_args(A, G, R, L.nin, L.nout, C, relu, res), L.w, L.b, L.x3);
     a.route_rows = route_rows;
-    a.in = A;
-    a.in_sn = a_gs;
-    a.in_sh = a_rs;
-    a.in_sw = 0;
-    a.H = R;
-    a.W = 1;
-    a.Cin = L.nin;
-    a.wgt = W(L.w);
-    a.ldb = L.nin;
-    a.bias = W(L.b);
-    a.res = res;
-    a.res_sn = r_gs;
-    a.res_sh = r_rs;
-    a.out = C;
-    a.out_sn = c_gs;
-    a.out_sh = c_rs;
-    a.out_sw = 0;
-    a.Nimg = G;
-    a.Ho = R;
-    a.Wo = 1;
-    a.Cout = L.nout;
-    a.relu = relu;
-    use_split(a, L.x3);
-    const double fl = 2.0 * G * R * (double)L.nout * L.nin;
-    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a);
+    run(a, 2.0 * G * R * (double)L.nout * L.nin);
   }
-
-  // C = A W^T + bias + res, and (when the GEMM can fuse it: conv_x3's quad epilogue with one N tile per row, Cout 64
-  // or 128) Y = LayerNorm(C) in the same pass, bit-identical to ln(); returns whether Y was written (otherwise the
-  // caller runs ln()). DDMI_LN_FOLD=0: never fused.
-  bool gemm_ln(const Lin& L, const float* A, int64_t lda, int M, float* C, int64_t ldc, const float* res, int64_t ldr,
-               const LNp& p, float* Y) {
-    ConvArgs a;
-    a.in = A;
-    a.in_sn = (int64_t)M * lda;
-    a.in_sh = lda;
-    a.in_sw = 0;
-    a.H = M;
-    a.W = 1;
-    a.Cin = L.nin;
-    a.wgt = W(L.w);
-    a.ldb = L.nin;
-    a.bias = W(L.b);
-    a.res = res;
-    a.res_sn = (int64_t)M * ldr;
-    a.res_sh = ldr;
-    a.out = C;
-    a.out_sn = (int64_t)M * ldc;
-    a.out_sh = ldc;
-    a.out_sw = 0;
-    a.Nimg = 1;
-    a.Ho = M;
-    a.Wo = 1;
-    a.Cout = L.nout;
-    use_split(a, L.x3);
-    if (ln_fold && p.c == L.nout) {
-      a.ln_out = Y;
-      a.ln_g = W(p.g);
-      a.ln_b = W(p.b);
-    }
-    const double fl = 2.0 * M * (double)L.nout * L.nin;
-    return launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a).ln;
+  // M dense rows, M * ld floats taken as the one group's stride
+  static View4 dense(const float* p, int M, int64_t ld) { return row_view(p, (int64_t)M * ld, ld); }
+  // dense rows: A [M][nin], C and res [M][nout]
+  void gemm(const Lin& L, const float* A, int M, float* C, bool relu = false, const float* res = nullptr) {
+    gemm_g(L, dense(A, M, L.nin), 1, M, dense(C, M, L.nout), relu, res ? dense(res, M, L.nout) : View4{});
   }
-
+  // The dense C = A W^T + bias + res, and (when the GEMM can fuse it: conv_x3's quad epilogue with one N tile per
+  // row, Cout 64 or 128) Y = LayerNorm(C) in the same pass, bit-identical to ln(); returns whether Y was written
+  // (otherwise the caller runs ln()). DDMI_LN_FOLD=0: never fused.
+  bool gemm_ln(const Lin& L, const float* A, int M, float* C, const float* res, const LNp& p, float* Y) {
+    ConvArgs a = attach(gemm_args(dense(A, M, L.nin), 1, M, L.nin, L.nout, dense(C, M, L.nout), false,
+                                  dense(res, M, L.nout)), L.w, L.b, L.x3);
+    if (ln_fold && p.c == L.nout) fold_ln(a, Y, W(p.g), W(p.b));
+    return run(a, 2.0 * M * (double)L.nout * L.nin).ln;
+  }
   // C = A[:, 0:kn] W[:, k0:k0+kn]^T (+bias when with_bias) (+res) (relu): a K-slice of a Linear (the weight
   // rows keep their full stride; 16-B aligned slices only)
-  void gemm_slice(const Lin& L, int k0, int kn, bool with_bias, const float* A, int64_t a_gs, int64_t a_rs, int G,
-                  int R, float* C, int64_t c_gs, int64_t c_rs, bool relu, const float* res, int64_t r_gs,
-                  int64_t r_rs) {
+  void gemm_slice(const Lin& L, int k0, int kn, bool with_bias, View4 A, int G, int R, View4 C, bool relu,
+                  View4 res = {}) {
     if (k0 % 8 || kn % 8 || k0 + kn > L.nin) throw std::runtime_error("gemm_slice: bad K slice");
-    ConvArgs a;
-    a.in = A;
-    a.in_sn = a_gs;
-    a.in_sh = a_rs;
-    a.in_sw = 0;
-    a.H = R;
-    a.W = 1;
-    a.Cin = kn;
-    a.wgt = W(L.w) + k0;
-    a.ldb = L.nin;
-    a.bias = with_bias ? W(L.b) : nullptr;
-    a.res = res;
-    a.res_sn = r_gs;
-    a.res_sh = r_rs;
-    a.out = C;
-    a.out_sn = c_gs;
-    a.out_sh = c_rs;
-    a.out_sw = 0;
-    a.Nimg = G;
-    a.Ho = R;
-    a.Wo = 1;
-    a.Cout = L.nout;
-    a.relu = relu;
-    use_split(a, L.x3);
-    if (a.wh) {
-      a.wh += k0;
-      if (L.x3.lo != kNone) a.wl += k0;
-    }
-    const double fl = 2.0 * G * R * (double)L.nout * kn;
-    launch(a.wh ? "conv_x3" : "conv_gemm", fl, [&] { return launch_conv_gemm(a, st); }, &a);
+    ConvArgs a = attach(gemm_args(A, G, R, kn, L.nout, C, relu, res), L.w, with_bias ? L.b : kNone, L.x3);
+    slice_k(a, k0, L.nin);
+    run(a, 2.0 * G * R * (double)L.nout * kn);
   }
 
   void ln(const LNp& p, const float* x, int64_t ldx, float* y, int64_t ldy, int rows, const float* res = nullptr,
@@ -1517,24 +1390,17 @@ class Model {
           conv_c(blk.ds, cur, nb, ch, cw, dsb, false);
           sc = dsb;
         }
-        const bool last = b + 1 == blocks.size();
-        auto request_pool = [&]() {  // square windows that tile the output exactly
-          if (!last || !pool || oh % pool->oh || ow % pool->ow || oh / pool->oh != ow / pool->ow) return;
-          pool_next = *pool;
-          pool_next_p = oh / pool->oh;
-        };
+        const PoolSpec* bp = b + 1 == blocks.size() ? pool : nullptr;  // the stage's final conv
+        ConvRoute r;
         if (!blk.bottleneck) {
           conv_c(blk.c1, cur, nb, ch, cw, tmp2, true);
-          request_pool();
-          conv_c(blk.c2, tmp2, nb, oh, ow, y, true, sc);
+          r = conv_c(blk.c2, tmp2, nb, oh, ow, y, true, sc, bp);
         } else {
           conv_c(blk.c1, cur, nb, ch, cw, tmp1, true);
           conv_c(blk.c2, tmp1, nb, ch, cw, tmp2, true);
-          request_pool();
-          conv_c(blk.c3, tmp2, nb, oh, ow, y, true, sc);
+          r = conv_c(blk.c3, tmp2, nb, oh, ow, y, true, sc, bp);
         }
-        if (last && pool) all_pooled = all_pooled && pool_done;
-        pool_next_p = 0;
+        if (bp) all_pooled = r.pooled;
         cur = y;
         ch = oh;
         cw = ow;
@@ -1551,28 +1417,11 @@ class Model {
   // the GPT token buffers of scale i (also the fused-pool targets of the stage's final convs)
   PoolSpec img_pool_spec(int i, int B) {
     const int C = gpt[i].C, T = 320;
-    PoolSpec p;
-    p.out = buf("gpt_x", (size_t)B * T * C);
-    p.sn = (int64_t)T * C;
-    p.sh = (int64_t)32 * C;
-    p.sw = C;
-    p.add = W(gpt[i].pos);
-    p.add_sh = (int64_t)32 * C;
-    p.add_sw = C;
-    p.oh = 8;
-    p.ow = 32;
-    return p;
+    return {hwc(buf("gpt_x", (size_t)B * T * C), (int64_t)T * C, 32, C), hwc(W(gpt[i].pos), 0, 32, C), 8, 32};
   }
   PoolSpec lid_pool_spec(int i, int B) {
     const int Cl = lid.ch[1 + i];
-    PoolSpec p;
-    p.out = buf("gpt_lpool", (size_t)B * 64 * Cl);
-    p.sn = (int64_t)64 * Cl;
-    p.sh = (int64_t)8 * Cl;
-    p.sw = Cl;
-    p.oh = 8;
-    p.ow = 8;
-    return p;
+    return {nhwc(buf("gpt_lpool", (size_t)B * 64 * Cl), 8, 8, Cl), View4{}, 8, 8};
   }
   void fuse(int i, float* imgf, int B, int Hi, int Wi, float* lidf, int Hl, int Wl, bool img_pooled = false,
             bool lid_pooled = false) {
@@ -1588,12 +1437,11 @@ class Model {
     float* LP = buf("gpt_lpool", (size_t)B * 64 * Cl);
     float* LO = buf("gpt_lout", (size_t)B * 64 * Cl);
     // tokens: pooled image (8x32) + pos_emb, then lidar_channel_to_img(pooled lidar 8x8) + pos_emb
-    View4 xo{X, (int64_t)T * C, (int64_t)32 * C, C, 1};
+    const View4 xo = hwc(X, (int64_t)T * C, 32, C), lpo = nhwc(LP, 8, 8, Cl);
     if (!img_pooled) launch("pool", 0, [&] { launch_avgpool(imgf, B, Hi, Wi, C, 8, 32, xo, W(g.pos), st); });
-    View4 lpo{LP, (int64_t)64 * Cl, (int64_t)8 * Cl, Cl, 1};
     if (!lid_pooled) launch("pool", 0, [&] { launch_avgpool(lidf, B, Hl, Wl, Cl, 8, 8, lpo, nullptr, st); });
-    conv(l2i[i], LP, (int64_t)64 * Cl, (int64_t)8 * Cl, Cl, B, 8, 8, X + (size_t)nimg * C, (int64_t)T * C,
-         (int64_t)8 * C, C, false, W(g.pos) + (size_t)nimg * C, 0, (int64_t)8 * C, C);
+    conv(l2i[i], lpo, B, 8, 8, hwc(X + (size_t)nimg * C, (int64_t)T * C, 8, C), false,
+         hwc(W(g.pos) + (size_t)nimg * C, 0, 8, C));
     const int M = B * T;
     // Hb = ln1(x) before each block's qkv, ln2(x) before its MLP, ln_f(x) at the end. Where the GEMM producing x
     // (proj, MLP-down) spans the row in one tile (C <= 128), its epilogue writes the LayerNorm too (gemm_ln)
@@ -1611,7 +1459,7 @@ class Model {
       const bool live = last_rows && bi + 1 == g.blocks.size();
       // (the Q third of this GEMM is dead for the image rows too; K | V over all rows + Q over the LiDAR rows as two
       // launches took 126 -> 85 + 20 us, which the bench did not show: profiles/gpt_last_rows.md)
-      gemm(w.qkv, Hb, C, M, QKV, 3 * C);
+      gemm(w.qkv, Hb, M, QKV);
       // softmax(Q K^T / sqrt(hs)) V per (scene, head), one fused launch (attention.hip): fp32 MFMA in the
       // fp32 mode, f16x3 MFMA in the f16x3 mode (two-way split scores) and the bf16 mode (three-way)
       const int aprec = (gemm_mode == DD_GEMM_FP32 || !gpt_attn_x3 || C / 4 > 128 || T % 32 || T > 1024)
@@ -1622,11 +1470,12 @@ class Model {
         const int64_t gs = (int64_t)T * C, off = (int64_t)nimg * C;
         launch("attn", 4.0 * B * nl * T * (double)C,
                [&] { launch_gpt_attention(QKV, B, T, C, 4, Y, aprec, st, nimg, nl); });
-        gemm_g(w.proj, Y + off, gs, C, B, nl, X + off, gs, C, false, X + off, gs, C, M);  // x = x + proj(y)
+        const View4 xl = row_view(X + off, gs, C), hl = row_view(Hb + off, gs, C);
+        gemm_g(w.proj, row_view(Y + off, gs, C), B, nl, xl, false, xl, M);  // x = x + proj(y)
         ln_g(w.ln2, X + off, Hb + off, C, B, nl, gs);
-        float* ML = MLP + (int64_t)nimg * 4 * C;
-        gemm_g(w.mlp0, Hb + off, gs, C, B, nl, ML, 4 * gs, 4 * C, true, nullptr, 0, 0, M);
-        gemm_g(w.mlp2, ML, 4 * gs, 4 * C, B, nl, X + off, gs, C, false, X + off, gs, C, M);  // x = x + mlp(ln2 x)
+        const View4 ml = row_view(MLP + (int64_t)nimg * 4 * C, 4 * gs, 4 * C);
+        gemm_g(w.mlp0, hl, B, nl, ml, true, {}, M);
+        gemm_g(w.mlp2, ml, B, nl, xl, false, xl, M);  // x = x + mlp(ln2 x)
         ln_g(g.lnf, X + off, Hb + off, C, B, nl, gs);
         hb_ready = true;
         continue;
@@ -1666,23 +1515,21 @@ class Model {
         hb_ready = true;
         continue;
       }
-      if (!gemm_ln(w.proj, Y, C, M, X, C, X, C, w.ln2, Hb))  // x = x + proj(y); Hb = ln2(x)
+      if (!gemm_ln(w.proj, Y, M, X, X, w.ln2, Hb))  // x = x + proj(y); Hb = ln2(x)
         ln(w.ln2, X, C, Hb, C, M);
-      gemm(w.mlp0, Hb, C, M, MLP, 4 * C, true);
-      hb_ready = gemm_ln(w.mlp2, MLP, 4 * C, M, X, C, X, C, nx, Hb);  // x = x + mlp(ln2 x); Hb = next LN(x)
+      gemm(w.mlp0, Hb, M, MLP, true);
+      hb_ready = gemm_ln(w.mlp2, MLP, M, X, X, nx, Hb);  // x = x + mlp(ln2 x); Hb = next LN(x)
     }
     if (!hb_ready) ln(g.lnf, X, C, Hb, C, M);  // Hb = ln_f(x): image tokens rows 0..255, lidar 256..319 per scene
-    conv(i2l[i], Hb + (size_t)nimg * C, (int64_t)T * C, (int64_t)8 * C, C, B, 8, 8, LO, (int64_t)64 * Cl,
-         (int64_t)8 * Cl, Cl, false);
+    const View4 gl = nhwc(LO, 8, 8, Cl);
+    conv(i2l[i], hwc(Hb + (size_t)nimg * C, (int64_t)T * C, 8, C), B, 8, 8, gl, false);
     // the image branch after the last fusion is never read (the BEV path takes the LiDAR features:
     // transformer_decoder_join, transfuser_backbone.py:204-205), so its upsample-add is skipped at i == 3
     if (i + 1 < 4) {
-      View4 gi{Hb, (int64_t)T * C, (int64_t)32 * C, C, 1};
-      View4 io{imgf, (int64_t)Hi * Wi * C, (int64_t)Wi * C, C, 1};
+      const View4 gi = hwc(Hb, (int64_t)T * C, 32, C), io = nhwc(imgf, Hi, Wi, C);
       launch("bilinear", 0, [&] { launch_bilinear(gi, B, 8, 32, C, io, Hi, Wi, 8.0f / Hi, 32.0f / Wi, 1, st); });
     }
-    View4 gl{LO, (int64_t)64 * Cl, (int64_t)8 * Cl, Cl, 1};
-    View4 lo{lidf, (int64_t)Hl * Wl * Cl, (int64_t)Wl * Cl, Cl, 1};
+    const View4 lo = nhwc(lidf, Hl, Wl, Cl);
     launch("bilinear", 0, [&] { launch_bilinear(gl, B, 8, 8, Cl, lo, Hl, Wl, 8.0f / Hl, 8.0f / Wl, 1, st); });
   }
 
@@ -1738,12 +1585,12 @@ class Model {
     for (int si = 0; si < steps; ++si) {
       const int k = roll[si];
       launch("misc", 0, [&] { launch_timestep_embed((float)k, te0, d, st); });
-      gemm(tm1, te0, d, 1, te1, 4 * d);
+      gemm(tm1, te0, 1, te1);
       launch("misc", 0, [&] { launch_activation(te1, te1, 4 * d, 0, st); });
-      gemm(tm3, te1, 4 * d, 1, te2, d);
+      gemm(tm3, te1, 1, te2);
       launch("misc", 0, [&] { launch_activation(te2, mte, d, 0, st); });
       for (int l = 0; l < 2; ++l)
-        gemm(dl[l].film, mte, d, 1, buf("film_s" + std::to_string(si) + "l" + std::to_string(l), 2 * d), 2 * d);
+        gemm(dl[l].film, mte, 1, buf("film_s" + std::to_string(si) + "l" + std::to_string(l), 2 * d));
     }
   }
 
@@ -1757,11 +1604,11 @@ class Model {
     float* te2 = buf("train_temb2", (size_t)B * d);
     float* mte = buf("train_temb_mish", (size_t)B * d);
     launch("misc", 0, [&] { launch_timestep_embed_rows(t, te0, B, d, st); });
-    gemm(tm1, te0, d, B, te1, 4 * d);
+    gemm(tm1, te0, B, te1);
     launch("misc", 0, [&] { launch_activation(te1, te1, (int64_t)B * 4 * d, 0, st); });
-    gemm(tm3, te1, 4 * d, B, te2, d);
+    gemm(tm3, te1, B, te2);
     launch("misc", 0, [&] { launch_activation(te2, mte, (int64_t)B * d, 0, st); });
-    for (int l = 0; l < 2; ++l) gemm(dl[l].film, mte, d, B, buf("train_film_l" + std::to_string(l), (size_t)B * 2 * d), 2 * d);
+    for (int l = 0; l < 2; ++l) gemm(dl[l].film, mte, B, buf("train_film_l" + std::to_string(l), (size_t)B * 2 * d));
     float* sa = buf("train_sa", B);
     float* s1a = buf("train_s1a", B);
     launch("misc", 0, [&] { launch_train_coeffs(t, ac_dev, sa, s1a, B, 1000, st); });
@@ -1831,9 +1678,9 @@ class Model {
 
     // ---- BEV tokens + status -> keyval (B, 65, 256) (+= _keyval_embedding)
     float* KV = buf("keyval", (size_t)B * 65 * d);
-    conv(bev_down, xl, (int64_t)Hl * Wl * 512, (int64_t)Wl * 512, 512, B, Hl, Wl, KV, (int64_t)65 * d, (int64_t)Wl * d,
-         d, false, W(kv_emb), 0, (int64_t)Wl * d, d);
-    gemm_g(status, stat, 8, 8, B, 1, KV + (size_t)64 * d, (int64_t)65 * d, d, false, W(kv_emb) + (size_t)64 * d, 0, d);
+    conv(bev_down, nhwc(xl, Hl, Wl, 512), B, Hl, Wl, hwc(KV, (int64_t)65 * d, Wl, d), false, hwc(W(kv_emb), 0, Wl, d));
+    gemm_g(status, row_view(stat, 8, 8), B, 1, row_view(KV + (size_t)64 * d, (int64_t)65 * d, d), false,
+           row_view(W(kv_emb) + (size_t)64 * d, 0, d));
 
     // ---- _tf_decoder: 3 post-norm layers over 31 queries, memory = keyval (:141-142), on the side
     // stream beside the FPN / bev_proj / value_proj chain below
@@ -1846,7 +1693,7 @@ class Model {
       if (tfdec_mk && tf_mk_layers && gemm_mode == DD_GEMM_F16X3) {
         // the memory's cross-attention K | V of all 3 layers in one GEMM, then one megakernel launch
         float* kvx = buf("tf_kvx", (size_t)B * 65 * 6 * d);
-        gemm(tf_cakv, KV, d, B * 65, kvx, 6 * d);
+        gemm(tf_cakv, KV, B * 65, kvx);
         TfMkArgs t;
         t.layers = tf_mk_layers;
         for (int l = 0; l < 2; ++l) {
@@ -1890,23 +1737,23 @@ class Model {
       float* ff = buf("tf_ff", (size_t)B * NQ * 1024);
       const int MQ = B * NQ;
       for (const TfLayerW& w : tf) {
-        gemm(w.sa_in, q, d, MQ, qkv, 3 * d);
+        gemm(w.sa_in, q, MQ, qkv);
         launch("mha", 0, [&] {
           launch_mha_small(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, att, d, B, NQ, NQ, 8, 32, (int64_t)NQ * 3 * d,
                            (int64_t)NQ * 3 * d, (int64_t)NQ * d, st);
         });
-        gemm(w.sa_out, att, d, MQ, tmp, d, false, q, d);
+        gemm(w.sa_out, att, MQ, tmp, false, q);
         ln(w.n1, tmp, d, q, d, MQ);
-        gemm(w.ca_q, q, d, MQ, qkv, d);
-        gemm(w.ca_kv, KV, d, B * 65, kvp, 2 * d);
+        gemm(w.ca_q, q, MQ, qkv);
+        gemm(w.ca_kv, KV, B * 65, kvp);
         launch("mha", 0, [&] {
           launch_mha_small(qkv, d, kvp, kvp + d, 2 * d, att, d, B, NQ, 65, 8, 32, (int64_t)NQ * d, (int64_t)65 * 2 * d,
                            (int64_t)NQ * d, st);
         });
-        gemm(w.ca_out, att, d, MQ, tmp, d, false, q, d);
+        gemm(w.ca_out, att, MQ, tmp, false, q);
         ln(w.n2, tmp, d, q, d, MQ);
-        gemm(w.l1, q, d, MQ, ff, 1024, true);
-        gemm(w.l2, ff, 1024, MQ, tmp, d, false, q, d);
+        gemm(w.l1, q, MQ, ff, true);
+        gemm(w.l2, ff, MQ, tmp, false, q);
         ln(w.n3, tmp, d, q, d, MQ);
       }
       // per decoder layer, step-invariant (exact hoists): ego cross-attention over ONE key =
@@ -1914,11 +1761,11 @@ class Model {
       for (int l = 0; l < 2; ++l) {
         const DiffLayerW& w = dl[l];
         float* e1 = buf("ego_v" + std::to_string(l), (size_t)B * d);
-        gemm_g(w.eg_v, q, (int64_t)NQ * d, d, B, 1, e1, d, d);
+        gemm_g(w.eg_v, row_view(q, (int64_t)NQ * d, d), B, 1, row_view(e1, d, d));
         egos[l] = buf("ego_out" + std::to_string(l), (size_t)B * d);
-        gemm(w.eg_out, e1, d, B, egos[l], d);
+        gemm(w.eg_out, e1, B, egos[l]);
         akv[l] = buf("agent_kv" + std::to_string(l), (size_t)B * 30 * 2 * d);
-        gemm_g(w.ag_kv, q + d, (int64_t)NQ * d, d, B, 30, akv[l], (int64_t)30 * 2 * d, 2 * d);
+        gemm_g(w.ag_kv, row_view(q + d, (int64_t)NQ * d, d), B, 30, row_view(akv[l], (int64_t)30 * 2 * d, 2 * d));
       }
     });
 
@@ -1929,24 +1776,23 @@ class Model {
     conv_c(c5, xl, B, Hl, Wl, p5, true);
     float* up2 = buf("p5_up", (size_t)B * Hl * 2 * Wl * 2 * bc);
     {
-      View4 a{p5, (int64_t)Hl * Wl * bc, (int64_t)Wl * bc, bc, 1};
-      View4 o{up2, (int64_t)4 * Hl * Wl * bc, (int64_t)2 * Wl * bc, bc, 1};
+      const View4 a = nhwc(p5, Hl, Wl, bc), o = nhwc(up2, 2 * Hl, 2 * Wl, bc);
       launch("bilinear", 0, [&] { launch_bilinear(a, B, Hl, Wl, bc, o, 2 * Hl, 2 * Wl, 0.5f, 0.5f, 0, st); });
     }
     float* p4 = buf("p4", (size_t)B * 4 * Hl * Wl * bc);
     conv_c(up5, up2, B, 2 * Hl, 2 * Wl, p4, true);
     float* up3 = buf("p4_up", (size_t)B * HB * WB * bc);
+    const View4 p4u = nhwc(up3, HB, WB, bc);
     {
-      View4 a{p4, (int64_t)4 * Hl * Wl * bc, (int64_t)2 * Wl * bc, bc, 1};
-      View4 o{up3, (int64_t)HB * WB * bc, (int64_t)WB * bc, bc, 1};
+      const View4 a = nhwc(p4, 2 * Hl, 2 * Wl, bc);
       launch("bilinear", 0, [&] {
-        launch_bilinear(a, B, 2 * Hl, 2 * Wl, bc, o, HB, WB, (float)(2 * Hl) / HB, (float)(2 * Wl) / WB, 0, st);
+        launch_bilinear(a, B, 2 * Hl, 2 * Wl, bc, p4u, HB, WB, (float)(2 * Hl) / HB, (float)(2 * Wl) / WB, 0, st);
       });
     }
     const int CC = 320;
     float* cross_in = buf("cross_in", (size_t)B * HB * WB * CC);
-    conv(up4, up3, (int64_t)HB * WB * bc, (int64_t)WB * bc, bc, B, HB, WB, cross_in + 256, (int64_t)HB * WB * CC,
-         (int64_t)WB * CC, CC, true);
+    const View4 catv = nhwc(cross_in, HB, WB, CC), p3 = channels_from(catv, 256);  // p3: channels 256..319
+    conv(up4, p4u, B, HB, WB, p3, true);
 
     const int MB = B * HB * WB;
     float* cross = buf("cross_bev", (size_t)MB * d);
@@ -1956,7 +1802,8 @@ class Model {
       // interpolation is linear with weights summing to 1, so the keyval half of the 320 -> 256 projection runs
       // on the 8 x 8 tokens and is upsampled into cross_bev, which the p3 half (K = 64) then adds to in place
       float* kvp = buf("kv_proj", (size_t)B * 64 * d);
-      gemm_slice(bevproj, 0, d, false, KV, (int64_t)65 * d, d, B, 64, kvp, (int64_t)64 * d, d, false, nullptr, 0, 0);
+      gemm_slice(bevproj, 0, d, false, row_view(KV, (int64_t)65 * d, d), B, 64, row_view(kvp, (int64_t)64 * d, d),
+                 false);
       if (bp_mode == 2) {
         // one pass: p3 in, cross_bev out (bevproj.hip)
         BevProjArgs a;
@@ -1977,19 +1824,17 @@ class Model {
         a.flags = num_flags;
         launch("bevproj", 2.0 * MB * 64 * d * 3, [&] { launch_bevproj(a, st); });
       } else {
-        View4 a{kvp, (int64_t)64 * d, (int64_t)8 * d, d, 1};
-        View4 o{cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, 1};
+        const View4 a = nhwc(kvp, 8, 8, d), o = nhwc(cross, HB, WB, d);
         launch("bilinear", 0, [&] { launch_bilinear(a, B, 8, 8, d, o, HB, WB, 8.0f / HB, 8.0f / WB, 0, st); });
-        gemm_slice(bevproj, d, CC - d, true, cross_in + d, (int64_t)MB * CC, CC, 1, MB, cross, (int64_t)MB * d, d,
-                   true, cross, (int64_t)MB * d, d);
+        const View4 cr = dense(cross, MB, d);
+        gemm_slice(bevproj, d, CC - d, true, dense(cross_in + d, MB, CC), 1, MB, cr, true, cr);
         ln(bevproj_ln, cross, d, cross, d, MB);
       }
     } else {
       // concat_cross_bev: keyval[:, :64] as (B,8,8,256) -> bilinear 64x64 -> channels 0..255
-      View4 a{KV, (int64_t)65 * d, (int64_t)8 * d, d, 1};
-      View4 o{cross_in, (int64_t)HB * WB * CC, (int64_t)WB * CC, CC, 1};
-      launch("bilinear", 0, [&] { launch_bilinear(a, B, 8, 8, d, o, HB, WB, 8.0f / HB, 8.0f / WB, 0, st); });
-      gemm(bevproj, cross_in, CC, MB, cross, d, true);
+      const View4 a = hwc(KV, (int64_t)65 * d, 8, d);
+      launch("bilinear", 0, [&] { launch_bilinear(a, B, 8, 8, d, catv, HB, WB, 8.0f / HB, 8.0f / WB, 0, st); });
+      gemm(bevproj, cross_in, MB, cross, true);
       ln(bevproj_ln, cross, d, cross, d, MB);
     }
 
@@ -2017,25 +1862,24 @@ class Model {
     side([&] {
       if (heads) {
         float* s1 = buf("sem_h", (size_t)B * HB * WB * bc);
-        conv(sem0, cross_in + 256, (int64_t)HB * WB * CC, (int64_t)WB * CC, CC, B, HB, WB, s1, (int64_t)HB * WB * bc,
-             (int64_t)WB * bc, bc, true);
+        const View4 s1v = nhwc(s1, HB, WB, bc);
+        conv(sem0, p3, B, HB, WB, s1v, true);
         float* s2 = buf("sem_logits", (size_t)B * HB * WB * 8);
-        conv(sem2, s1, (int64_t)HB * WB * bc, (int64_t)WB * bc, bc, B, HB, WB, s2, (int64_t)HB * WB * 7, (int64_t)WB * 7, 7,
-             false);
+        const View4 a = nhwc(s2, HB, WB, 7);
+        conv(sem2, s1v, B, HB, WB, a, false);
         const int SH = HL / 2, SW = WL;
         float* sem = buf("bev_semantic_map", (size_t)B * 7 * SH * SW);
-        View4 a{s2, (int64_t)HB * WB * 7, (int64_t)WB * 7, 7, 1};
         View4 o{sem, (int64_t)7 * SH * SW, SW, 1, (int64_t)SH * SW};
         launch("bilinear", 0, [&] {
           launch_bilinear(a, B, HB, WB, 7, o, SH, SW, (float)HB / SH, (float)WB / SW, 0, st);
         });
         float* a1 = buf("agent_h", (size_t)B * 30 * 1024);
-        gemm_g(ag0, agents, (int64_t)NQ * d, d, B, 30, a1, (int64_t)30 * 1024, 1024, true);
+        gemm_g(ag0, row_view(agents, (int64_t)NQ * d, d), B, 30, row_view(a1, (int64_t)30 * 1024, 1024), true);
         float* ast = buf("agent_states", (size_t)B * 30 * 5);
-        gemm(ag2, a1, 1024, B * 30, ast, 5);
+        gemm(ag2, a1, B * 30, ast);
         launch("misc", 0, [&] { launch_agent_post(ast, B * 30, st); });
         float* alb = buf("agent_labels", (size_t)B * 30);
-        gemm_g(agl, agents, (int64_t)NQ * d, d, B, 30, alb, 30, 1);
+        gemm_g(agl, row_view(agents, (int64_t)NQ * d, d), B, 30, row_view(alb, 30, 1));
       }
     });
 
@@ -2174,15 +2018,9 @@ class Model {
           });
         }
         vslots_l[l] = slots;
-        ConvArgs a = conv_args(dl[l].vproj, cross, (int64_t)HB * WB * d, (int64_t)WB * d, d, D / S, HB, WB, vrows,
-                               (int64_t)MR * d, d, 0, true, nullptr, 0, 0, 0);
-        a.Nimg = 1;
-        a.Ho = MR;
-        a.Wo = 1;
-        a.rowmap = rows;
-        a.rowmap_nimg = D / S;  // the images of `cross`; the rows are the D decoder scenes' taps
-        const double fl = 2.0 * MR * (double)d * 9 * dl[l].vproj.cin_real;
-        launch("conv_x3", fl, [&] { return launch_conv_gemm(a, st); }, &a);
+        // D / S: the images of `cross`; the rows are the D decoder scenes' taps
+        run(value_rows_args(dl[l].vproj, cross, D / S, HB, WB, rows, MR, vrows),
+            2.0 * MR * (double)d * 9 * dl[l].vproj.cin_real);
         vrows_l[l] = vrows;
       };
       if (gathered) {
@@ -2193,9 +2031,9 @@ class Model {
           side([&] { gather_value(0, pts); });
         }
       }
-      gemm(pa0, emb, 512, R, tf1, d, true);
+      gemm(pa0, emb, R, tf1, true);
       ln(pa2, tf1, d, tf1, d, R);
-      gemm(pa3, tf1, d, R, tfe, d);
+      gemm(pa3, tf1, R, tfe);
       const float* cur = pts;
       for (int l = 0; l < 2; ++l) {
         const DiffLayerW& w = dl[l];
@@ -2204,7 +2042,7 @@ class Model {
         // per-(step, layer) buffer: the cls branch of this layer reads it beside the next layer
         float* x2 = buf("dx2" + sfx, (size_t)R * d);
         // GridSampleCrossBEVAttention
-        gemm(w.attw, tfe, d, R, logit, P);
+        gemm(w.attw, tfe, R, logit);
         float* gso = buf("gs" + sfx, (size_t)R * d);
         if (gathered) {
           if (l == 0) {
@@ -2222,9 +2060,9 @@ class Model {
             launch_bev_sample_attn(logit, cur, vals[l], gso, D, Q, P, HB, WB, d, 1.0f / 32.0f, 1.0f / 32.0f, st, S);
           });
         }
-        gemm(w.outp, gso, d, R, x1, d, false, tfe, d);
+        gemm(w.outp, gso, R, x1, false, tfe);
         // cross_agent_attention + norm1
-        gemm(w.ag_q, x1, d, R, qa, d);
+        gemm(w.ag_q, x1, R, qa);
         if (tf_pending) {
           join();  // tf decoder: agent K / V and ego rows of both layers
           tf_pending = false;
@@ -2233,13 +2071,13 @@ class Model {
           launch_mha_small(qa, d, akv[l], akv[l] + d, 2 * d, gs, d, D, Q, 30, 8, 32, (int64_t)Q * d,
                            (int64_t)30 * 2 * d, (int64_t)Q * d, st, S);
         });
-        gemm(w.ag_out, gs, d, R, x2, d, false, x1, d);
+        gemm(w.ag_out, gs, R, x2, false, x1);
         ln(w.n1, x2, d, x2, d, R);
         // cross_ego_attention (hoisted, exact) + norm2
         ln(w.n2, x2, d, x3, d, R, egos[l], d, Q * S);  // row r: scene r / Q / S
         // ffn -> norm3 -> FiLM time modulation
-        gemm(w.ffn0, x3, d, R, hf, 1024, true);
-        gemm(w.ffn2, hf, 1024, R, x2, d);
+        gemm(w.ffn0, x3, R, hf, true);
+        gemm(w.ffn2, hf, R, x2);
         if (c.train) {  // one FiLM vector per scene (its Q rows)
           const float* fl = bufs.at("train_film_l" + std::to_string(l)).first;
           ln(w.n3, x2, d, x2, d, R, nullptr, 0, 1, fl, fl + d, Q, 2 * d);
@@ -2250,17 +2088,17 @@ class Model {
         float* cls = buf("cls" + sfx, R);
         fork();
         side([&] {
-          gemm(w.c0, x2, d, R, c1, d, true);
+          gemm(w.c0, x2, R, c1, true);
           ln(w.c2, c1, d, c1, d, R);
-          gemm(w.c3, c1, d, R, c2, d, true);
+          gemm(w.c3, c1, R, c2, true);
           ln(w.c5, c2, d, c2, d, R);
-          gemm(w.c6, c2, d, R, cls, 1);
+          gemm(w.c6, c2, R, cls);
         });
         float* reg = buf("reg" + sfx, (size_t)R * P * 3);
         float* nxt = (l == 0) ? pts2 : nullptr;
-        gemm(w.r0, x2, d, R, r1, d, true);
-        gemm(w.r2, r1, d, R, r2, d, true);
-        gemm(w.r4, r2, d, R, rr, P * 3);
+        gemm(w.r0, x2, R, r1, true);
+        gemm(w.r2, r1, R, r2, true);
+        gemm(w.r4, r2, R, rr);
         launch("misc", 0, [&] { launch_reg_finalize(rr, cur, reg, nxt, R, P, st); });
         cur = pts2;
         reg_last = reg;

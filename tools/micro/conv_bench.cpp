@@ -119,33 +119,11 @@ int main(int argc, char** argv) {
     Arena ar;
     const SplitW x = prep_split(ar, hw.data(), sh.Cout, K);
     ar.upload();
-    ConvArgs a;
-    a.in = din;
-    a.in_sw = sh.Cin;
-    a.in_sh = (int64_t)sh.W * sh.Cin;
-    a.in_sn = (int64_t)sh.H * sh.W * sh.Cin;
-    a.H = sh.H;
-    a.W = sh.W;
-    a.Cin = sh.Cin;
+    ConvArgs a = conv_args(nhwc(din, sh.H, sh.W, sh.Cin), sh.B, sh.H, sh.W, sh.Cin,
+                           ConvGeom{sh.k, sh.k, sh.s, pad, sh.Cout}, nhwc(dref, Ho, Wo, sh.Cout), 1,
+                           nhwc(dres, Ho, Wo, sh.Cout));
     a.wgt = dw;
-    a.ldb = K;
     a.bias = db;
-    a.Nimg = sh.B;
-    a.Ho = Ho;
-    a.Wo = Wo;
-    a.Cout = sh.Cout;
-    a.out = dref;
-    a.out_sw = sh.Cout;
-    a.out_sh = (int64_t)Wo * sh.Cout;
-    a.out_sn = (int64_t)Ho * Wo * sh.Cout;
-    a.res = dres;
-    a.res_sw = a.out_sw;
-    a.res_sh = a.out_sh;
-    a.res_sn = a.out_sn;
-    a.KH = a.KW = sh.k;
-    a.stride = sh.s;
-    a.pad = pad;
-    a.relu = 1;
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
