@@ -73,6 +73,16 @@ class DDSimParams(ctypes.Structure):
     ]
 
 
+class DDComfortParams(ctypes.Structure):
+    """dd_comfort_params: dt and the seven comfort bounds of dd_comfort; a bound of 0 is no bound (include/ddmi.h)."""
+    _fields_ = [
+        ("dt", ctypes.c_double), ("min_lon_accel", ctypes.c_double), ("max_lon_accel", ctypes.c_double),
+        ("max_abs_lat_accel", ctypes.c_double), ("max_abs_mag_jerk", ctypes.c_double),
+        ("max_abs_lon_jerk", ctypes.c_double), ("max_abs_yaw_accel", ctypes.c_double),
+        ("max_abs_yaw_rate", ctypes.c_double),
+    ]
+
+
 MAX_SAMPLES = 32  # DD_MAX_SAMPLES
 
 # name -> (restype, argtypes)
@@ -118,6 +128,9 @@ _SIGS = {
                                              ctypes.POINTER(DDSimParams), c_void_p, c_void_p, c_void_p]),
     "dd_simulate": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int, ctypes.c_int,
                                    ctypes.POINTER(DDSimParams), c_void_p, c_void_p, c_void_p]),
+    "dd_default_comfort_params": (None, [ctypes.POINTER(DDComfortParams)]),
+    "dd_comfort": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.POINTER(DDComfortParams), c_void_p, c_void_p,
+                                  c_void_p]),
     "dd_set_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_set_schedule": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_get_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int)]),

@@ -187,6 +187,17 @@ class DiffusionDriveAgent(_Base):
             traj = traj.to(torch.device("cuda", self._transfuser_model.device))
         return simulate_trajectories(traj, ego_states, params)
 
+    def comfort_metrics(self, states: torch.Tensor, params=None, signals: bool = False):
+        """The comfort sub-score of the PDM score on the GPU (``diffusiondrive_amd.simulate.comfort_metrics``): the six
+        flags (..., 6) bool of ``ego_is_comfortable`` (pdm_comfort_metrics.py:313-336) for the (..., 41, 11) float64
+        states ``simulate_trajectories`` returns, read in place; with ``signals`` also the six filtered series. A host
+        tensor is moved to the model's device."""
+        from .simulate import comfort_metrics
+        states = torch.as_tensor(states)
+        if states.device.type != "cuda":
+            states = states.to(torch.device("cuda", self._transfuser_model.device))
+        return comfort_metrics(states, params, signals)
+
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).
 TransfuserAgent = DiffusionDriveAgent

@@ -18,6 +18,7 @@
   } while (0)
 
 struct dd_sim_params;  // include/ddmi.h
+struct dd_comfort_params;
 
 namespace ddmi {
 
@@ -618,5 +619,10 @@ void launch_bev_ce(const float* logits, const uint8_t* target, float* part, floa
 size_t simulate_work_doubles(int N);
 void launch_simulate(const float* traj, const double* proposals, const double* ego_states, int N, int per_group,
                      const dd_sim_params& p, double* work, double* out_states, hipStream_t st);
+
+// ---- comfort.hip: PDM comfort metrics (dd_comfort) of (N, 41, 11) states: out_flags (N, 6), out_signals (N, 6, 41)
+// or null. One launch; the parameters are checked by the caller.
+void launch_comfort(const double* states, int N, const dd_comfort_params& p, uint8_t* out_flags, double* out_signals,
+                    hipStream_t st);
 
 }  // namespace ddmi

@@ -2639,6 +2639,48 @@ int dd_simulate(const float* traj, int num_poses, const double* ego_states, int 
                         out_states, stream);
 }
 
+// ---- comfort metrics (comfort.hip): stateless, every argument checked before any device work
+void dd_default_comfort_params(dd_comfort_params* p) {
+  if (!p) return;
+  p->dt = 0.1;
+  p->min_lon_accel = -4.05;
+  p->max_lon_accel = 2.40;
+  p->max_abs_lat_accel = 4.89;
+  p->max_abs_mag_jerk = 8.37;
+  p->max_abs_lon_jerk = 4.13;
+  p->max_abs_yaw_accel = 1.93;
+  p->max_abs_yaw_rate = 0.95;
+}
+
+int dd_comfort(const double* states, int N, const dd_comfort_params* p, uint8_t* out_flags, double* out_signals,
+               void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_comfort: " + what); };
+    if (N <= 0) bad("N = " + std::to_string(N) + " must be positive");
+    if (!states) bad("states is null");
+    if (!p) bad("params is null");
+    if (!out_flags) bad("out_flags is null");
+    if (!(p->dt > 0.0) || !std::isfinite(p->dt))
+      bad("dd_comfort_params.dt = " + std::to_string(p->dt) + " must be positive and finite");
+    const struct { const char* field; double v; } bounds[] = {
+        {"min_lon_accel", p->min_lon_accel},         {"max_lon_accel", p->max_lon_accel},
+        {"max_abs_lat_accel", p->max_abs_lat_accel}, {"max_abs_mag_jerk", p->max_abs_mag_jerk},
+        {"max_abs_lon_jerk", p->max_abs_lon_jerk},   {"max_abs_yaw_accel", p->max_abs_yaw_accel},
+        {"max_abs_yaw_rate", p->max_abs_yaw_rate}};
+    for (const auto& b : bounds)
+      if (std::isnan(b.v)) bad(std::string("dd_comfort_params.") + b.field + " is NaN");
+    // a bound of exactly 0 is no bound (ddmi.h); two real bounds must leave an interval
+    if (p->min_lon_accel != 0.0 && p->max_lon_accel != 0.0 && p->min_lon_accel >= p->max_lon_accel)
+      bad("dd_comfort_params.min_lon_accel = " + std::to_string(p->min_lon_accel) + " is not below max_lon_accel = " +
+          std::to_string(p->max_lon_accel));
+    for (int k = 2; k < 7; ++k)
+      if (bounds[k].v < 0.0)
+        bad(std::string("dd_comfort_params.") + bounds[k].field + " = " + std::to_string(bounds[k].v) +
+            " is negative (the bounds are -v and +v)");
+    ddmi::launch_comfort(states, N, *p, out_flags, out_signals, static_cast<hipStream_t>(stream));
+  });
+}
+
 int dd_set_profiling(dd_handle* h, int enable) {
   return guarded([&] {
     if (!h) throw std::invalid_argument("null handle");

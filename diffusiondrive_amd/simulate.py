@@ -4,11 +4,13 @@ The PDM score (navsim/evaluate/pdm_score.py:83-140) scores the states ``PDMSimul
 from a planner's trajectory, never the waypoints themselves. ``simulate_trajectories`` runs that simulation for every
 candidate of a device tensor in one launch sequence - ``trajectory`` (B, 8, 3), ``poses_reg`` (B, 20, 8, 3) or the
 samples outputs (B, S, 20, 8, 3), read in place - in float64 as the reference does; ``simulate_proposals`` takes
-41-pose proposals that are already on the 0.1 s grid. The sub-scores themselves are out of scope. There is no CPU
-fallback: a missing library or device raises.
+41-pose proposals that are already on the 0.1 s grid. ``comfort_metrics`` scores the comfort sub-score of those states
+on the device (``dd_comfort``: the six flags of ``ego_is_comfortable``, pdm_comfort_metrics.py:313-336); the other
+sub-scores need the map and the observations and are out of scope. There is no CPU fallback: a missing library or
+device raises.
 """
 import ctypes
-from typing import Mapping, Optional, Union
+from typing import Mapping, Optional, Tuple, Union
 
 import torch
 
@@ -17,6 +19,7 @@ from . import _lib
 NUM_POSES = 8    # planner poses per candidate (0.5 s apart)
 NUM_STATES = 41  # simulated states per candidate (0.1 s apart, the start state first)
 STATE_SIZE = 11  # StateIndex of pdm_enums.py: x, y, heading, vx, vy, ax, ay, steering angle / rate, yaw rate / accel
+NUM_COMFORT = 6  # lon / lat acceleration, jerk magnitude, lon jerk, yaw acceleration, yaw rate (the reference's order)
 
 
 def default_params(lib=None) -> _lib.DDSimParams:
@@ -112,3 +115,57 @@ def simulate_proposals(proposals: torch.Tensor, ego_states: torch.Tensor, params
         return lib.dd_simulate_proposals(src.data_ptr(), ego_t.data_ptr(), n_, pg, p, work, out, s)
 
     return _run(entry, lib, proposals, ego, n, int(per_group), params, stream)
+
+
+def default_comfort_params(lib=None) -> _lib.DDComfortParams:
+    """``dd_default_comfort_params``: dt = 0.1 s and the reference's seven bounds (pdm_comfort_metrics.py:11-28)."""
+    p = _lib.DDComfortParams()
+    (lib or _lib.load()).dd_default_comfort_params(ctypes.byref(p))
+    return p
+
+
+def _comfort_params(params: Union[None, _lib.DDComfortParams, Mapping], lib) -> _lib.DDComfortParams:
+    if isinstance(params, _lib.DDComfortParams):
+        return params
+    p = default_comfort_params(lib)
+    for k, v in (params or {}).items():
+        if k not in dict(p._fields_):
+            raise ValueError(f"unknown comfort parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def comfort_metrics(states: torch.Tensor, params=None, signals: bool = False,
+                    stream: Optional[torch.cuda.Stream] = None
+                    ) -> Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]]:
+    """``ego_is_comfortable`` (pdm_comfort_metrics.py:313-336) on the device. ``states``: device float64
+    (..., 41, 11), exactly what ``simulate_trajectories`` / ``simulate_proposals`` return, read in place. Returns
+    ``flags`` (..., 6) torch.bool - lon acceleration, lat acceleration, jerk magnitude, lon jerk, yaw acceleration, yaw
+    rate within their bounds at every sample - or ``(flags, signals)`` with the six rounded series (..., 6, 41) float64
+    the flags are taken from. ``params``: a ``DDComfortParams`` or a mapping of overrides of the reference's values; a
+    bound of exactly 0 means no bound on that side, as in the reference. A bad argument raises ``ValueError`` with
+    ``dd_last_error()``'s text."""
+    lib = _lib.load()
+    if not isinstance(states, torch.Tensor) or states.device.type != "cuda":
+        raise ValueError("states must be a device tensor (simulate_trajectories' / simulate_proposals' output)")
+    if states.dtype != torch.float64 or states.dim() < 2 or tuple(states.shape[-2:]) != (NUM_STATES, STATE_SIZE):
+        raise ValueError(f"states must be float64 (..., {NUM_STATES}, {STATE_SIZE}), got {tuple(states.shape)} "
+                         f"{states.dtype}")
+    states = states.contiguous()
+    lead = tuple(states.shape[:-2])
+    n = 1
+    for d in lead:
+        n *= d
+    dev = states.device
+    p = _comfort_params(params, lib)
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):  # the outputs belong to the stream that runs
+        flags = torch.empty((*lead, NUM_COMFORT), dtype=torch.uint8, device=dev)
+        sig = torch.empty((*lead, NUM_COMFORT, NUM_STATES), dtype=torch.float64, device=dev) if signals else None
+        rc = lib.dd_comfort(states.data_ptr(), n, ctypes.byref(p), flags.data_ptr(),
+                            sig.data_ptr() if signals else None, s.cuda_stream)
+    if rc == -1:  # DD_ERR_INVALID
+        raise ValueError((lib.dd_last_error() or b"").decode(errors="replace"))
+    _lib.check(rc, lib)
+    flags = flags.view(torch.bool)
+    return (flags, sig) if signals else flags

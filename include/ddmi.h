@@ -27,6 +27,8 @@
  *                  batch_kinematic_bicycle.py:76-185), the first stage of the PDM score (pdm_score.py:83-140)
  *   dd_simulate  <- transform_trajectory + get_trajectory_as_array (pdm_score.py:24-80) on the planner's 8 poses,
  *                  then the same simulation
+ *   dd_comfort   <- ego_is_comfortable                          pdm_planner/scoring/pdm_comfort_metrics.py:313-336
+ *                  (the six comfort flags of the simulated states, and optionally the six filtered signals)
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
  * handle must be serialised by the caller (the reference runs one agent per worker process,
@@ -300,8 +302,9 @@ int dd_tap(dd_handle* h, const char* name, float* dst, size_t count, size_t* act
  * 41-state proposal at 0.1 s and runs PDMSimulator.simulate_proposals - an LQR tracker closed over a kinematic bicycle
  * model for 40 steps - and computes every sub-score from the simulated states. These entries run that simulation for N
  * candidates (dd_forward_samples draws up to 32 x 20 per scene) without a handle, in float64 throughout as the
- * reference does, deterministically (no atomics; two calls on the same input are bit-equal). The sub-scores themselves
- * (collision, drivable area, progress, TTC, comfort) are out of scope. */
+ * reference does, deterministically (no atomics; two calls on the same input are bit-equal). Of the sub-scores, comfort
+ * is in scope (dd_comfort below: it needs nothing but the states); the others (collision, drivable area, progress, TTC)
+ * need the map and the observations and are out of scope. */
 typedef struct dd_sim_params {
   double wheel_base;                /* 3.089 m (nuPlan's get_pacifica_parameters) */
   double dt;                        /* 0.1 s: the proposal's sampling interval and the tracker's discretisation; the
@@ -349,6 +352,46 @@ int dd_simulate_proposals(const double* proposals, const double* ego_states, int
  * num_poses must be 8 (poses at 0.5 s: the only num_poses dd_create accepts), else DD_ERR_INVALID. */
 int dd_simulate(const float* traj, int num_poses, const double* ego_states, int N, int per_group,
                 const dd_sim_params* params, double* work, double* out_states, void* stream);
+
+/* ---- comfort metrics of simulated states (ego_is_comfortable, pdm_comfort_metrics.py:313-336, on the GPU) ------ */
+/* The bounds are the module constants of pdm_comfort_metrics.py:11-28. A bound of exactly 0 (either sign) means NO
+ * bound on that side: the reference's _within_bound tests the bound's truthiness (`min_bound if min_bound else -inf`,
+ * :216-217), and dd_comfort keeps that. The symmetric bounds are used as (-b, +b). */
+typedef struct dd_comfort_params {
+  double dt;                 /* 0.1 s between states; delta = mean(diff(arange(41) * dt)) as the reference forms it */
+  double min_lon_accel;      /* -4.05 m/s^2 */
+  double max_lon_accel;      /*  2.40 m/s^2 */
+  double max_abs_lat_accel;  /*  4.89 m/s^2 */
+  double max_abs_mag_jerk;   /*  8.37 m/s^3 */
+  double max_abs_lon_jerk;   /*  4.13 m/s^3 */
+  double max_abs_yaw_accel;  /*  1.93 rad/s^2 */
+  double max_abs_yaw_rate;   /*  0.95 rad/s */
+} dd_comfort_params;
+/* Fill *p with the reference's values listed above. */
+void dd_default_comfort_params(dd_comfort_params* p);
+/* states: device double (N, 41, 11) in StateIndex order, exactly what dd_simulate / dd_simulate_proposals write (read
+ * in place: heading = column 2, acceleration x / y = columns 5 / 6). out_flags: device uint8 (N, 6), 1 = every sample
+ * of the signal satisfies lo < v < hi (false on NaN), in the reference's order; out_signals: device double (N, 6, 41)
+ * or NULL, the six signals the flags are taken from, each np.round(., 8) = rint(v * 1e8) / 1e8:
+ *   0 lon acceleration  savgol(ax, window 41, order 2)                                   (min_lon_accel, max_lon_accel)
+ *   1 lat acceleration  savgol(ay, window 41, order 2)                                   +-max_abs_lat_accel
+ *   2 jerk magnitude    savgol(round(savgol(hypot(ax, ay), window 8, order 2)), window 41, order 2, deriv 1, delta)
+ *                                                                                        +-max_abs_mag_jerk
+ *   3 lon jerk          the same with ax in place of the hypot                           +-max_abs_lon_jerk
+ *   4 yaw acceleration  savgol(unwrap(heading), window 5, order 3, deriv 2, delta)       +-max_abs_yaw_accel
+ *   5 yaw rate          savgol(unwrap(heading), window 5, order 2, deriv 1, delta)       +-max_abs_yaw_rate
+ * as the reference really computes them: the yaw signals use window 5 whatever window_length says (:110-136 never
+ * passes it on), the jerk signals pre-smooth with the EVEN window 8 (:98; scipy fits the quadratic half a sample off
+ * the grid: output i reads samples i-3..i+4) and round before differentiating, savgol_filter runs in mode "interp"
+ * (the first and last window / 2 outputs come from the polynomial fitted to the first / last window samples; with
+ * window 41 every output is one fit of the whole series), and unwrap is _phase_unwrap (:139-157): heading - 2 pi
+ * cumsum(rint(diff(heading) / 2 pi)), ties to even. A non-finite input sample makes every output it reaches
+ * non-finite and the flags that read them 0; nothing is raised. One launch on `stream`; the call allocates nothing,
+ * copies nothing and does not synchronise. DD_ERR_INVALID before any device work, with the argument or field named
+ * in dd_last_error(): N <= 0, null states / params / out_flags, dt <= 0 or non-finite, a NaN bound, a lower bound >=
+ * its upper bound when both are non-zero (a negative symmetric bound, or min_lon_accel >= max_lon_accel). */
+int dd_comfort(const double* states, int N, const dd_comfort_params* params, uint8_t* out_flags, double* out_signals,
+               void* stream);
 
 /* ---- input feature builder (TransfuserFeatureBuilder.compute_features on the GPU) ---------- */
 /* Camera feature (transfuser_features.py:57-77): crop + stitch + cv2 INTER_LINEAR resize +
