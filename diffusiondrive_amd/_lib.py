@@ -83,6 +83,27 @@ class DDComfortParams(ctypes.Structure):
     ]
 
 
+class DDOpView(ctypes.Structure):
+    """dd_op_view: a strided (n, h, w, c) operand of the view-taking single-op entries (include/ddmi.h)."""
+    _fields_ = [("p", c_void_p), ("sn", ctypes.c_int64), ("sh", ctypes.c_int64), ("sw", ctypes.c_int64),
+                ("sc", ctypes.c_int64)]
+
+
+class DDOpConvDesc(ctypes.Structure):
+    """dd_op_conv_desc: one conv / GEMM launch of dd_op_conv_view (include/ddmi.h)."""
+    _fields_ = [
+        ("in_", DDOpView), ("out", DDOpView), ("res", DDOpView),
+        ("N", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int), ("Cin", ctypes.c_int),
+        ("KH", ctypes.c_int), ("KW", ctypes.c_int), ("stride", ctypes.c_int), ("pad", ctypes.c_int),
+        ("Cout", ctypes.c_int),
+        ("wgt", c_void_p), ("ldb", ctypes.c_int64), ("k0", ctypes.c_int), ("bias", c_void_p),
+        ("relu", ctypes.c_int), ("mode", ctypes.c_int), ("flags", c_void_p), ("route_rows", ctypes.c_int64),
+        ("ln_out", c_void_p), ("ln_g", c_void_p), ("ln_b", c_void_p),
+        ("pool_out", DDOpView), ("pool_p", ctypes.c_int), ("pool_add", DDOpView),
+        ("fused_ln", ctypes.c_int), ("fused_pool", ctypes.c_int),
+    ]
+
+
 MAX_SAMPLES = 32  # DD_MAX_SAMPLES
 
 # name -> (restype, argtypes)
@@ -196,6 +217,14 @@ _SIGS = {
                                                 c_void_p]),
     "dd_op_layernorm_groups": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
                                               ctypes.c_longlong, ctypes.c_int, c_void_p]),
+    "dd_op_conv_desc_size": (ctypes.c_size_t, []),
+    "dd_op_conv_view": (ctypes.c_int, [ctypes.POINTER(DDOpConvDesc), c_void_p]),
+    "dd_op_layernorm_ld": (ctypes.c_int, [c_void_p, ctypes.c_int64, c_void_p, ctypes.c_int64, ctypes.c_int, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int64, c_void_p,
+                                          ctypes.c_int64, ctypes.c_int, ctypes.c_int, c_void_p]),
+    "dd_op_bilinear_view": (ctypes.c_int, [ctypes.POINTER(DDOpView), ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, ctypes.POINTER(DDOpView), ctypes.c_int, ctypes.c_int,
+                                           ctypes.c_int, c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

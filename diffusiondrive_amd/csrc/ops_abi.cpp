@@ -406,4 +406,91 @@ int dd_op_layernorm_groups(const float* x, const float* g, const float* b, float
   });
 }
 
+size_t dd_op_conv_desc_size(void) { return sizeof(dd_op_conv_desc); }
+
+static View4 view_of(const dd_op_view& v) { return {v.p, v.sn, v.sh, v.sw, v.sc}; }
+
+int dd_op_conv_view(dd_op_conv_desc* d, void* stream) {
+  return op_guard([&] {
+    if (!d) throw std::invalid_argument("dd_op_conv_view: null descriptor");
+    d->fused_ln = d->fused_pool = 0;
+    if (!d->in.p || !d->out.p || !d->wgt) throw std::invalid_argument("dd_op_conv_view: null in, out or wgt");
+    if (d->mode < 0 || d->mode > 2) throw std::invalid_argument("dd_op_conv_view: mode must be 0, 1 or 2");
+    if (d->N < 1 || d->H < 1 || d->W < 1 || d->Cin < 1 || d->Cout < 1 || d->KH < 1 || d->KW < 1 || d->stride < 1 ||
+        d->pad < 0)
+      throw std::invalid_argument("dd_op_conv_view: bad geometry");
+    for (const dd_op_view* v : {&d->in, &d->out, &d->res, &d->pool_out, &d->pool_add})
+      if (v->p && v->sc != 1) throw std::invalid_argument("dd_op_conv_view: the operands' channel stride is 1");
+    const int64_t K = (int64_t)d->KH * d->KW * d->Cin;
+    const bool sliced = d->k0 != 0 || d->ldb != K;
+    if (sliced && (d->KH != 1 || d->KW != 1 || d->k0 < 0 || d->k0 % 8 || d->Cin % 8 || d->k0 + K > d->ldb))
+      throw std::invalid_argument("dd_op_conv_view: a K slice needs a 1 x 1 geometry, k0 % 8 == 0, Cin % 8 == 0 and "
+                                  "k0 + Cin <= ldb");
+    const ConvGeom g{d->KH, d->KW, d->stride, d->pad, d->Cout};
+    const bool rows = d->KH == 1 && d->KW == 1 && d->stride == 1 && d->pad == 0 && d->W == 1;
+    ConvArgs a = rows ? gemm_args(view_of(d->in), d->N, d->H, d->Cin, d->Cout, view_of(d->out), d->relu,
+                                  view_of(d->res))
+                      : conv_args(view_of(d->in), d->N, d->H, d->W, d->Cin, g, view_of(d->out), d->relu,
+                                  view_of(d->res));
+    a.wgt = d->wgt;
+    a.bias = d->bias;
+    a.route_rows = d->route_rows;
+    // modes 1 / 2: the whole weight (every K of its rows) split on the host exactly as dd_create does
+    Arena ar;
+    DD_HIP_CHECK(hipStreamSynchronize(S(stream)));
+    if (d->mode) {
+      std::vector<float> hw((size_t)d->Cout * d->ldb);
+      DD_HIP_CHECK(hipMemcpy(hw.data(), d->wgt, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
+      const SplitW x = prep_split(ar, hw.data(), d->Cout, (int)d->ldb);
+      ar.upload();
+      attach_split(a, ar, x, d->mode - 1, d->flags);
+    }
+    if (sliced) slice_k(a, d->k0, d->ldb);
+    if (d->ln_out) fold_ln(a, d->ln_out, d->ln_g, d->ln_b);
+    if (d->pool_out.p) pool_into(a, d->pool_p, view_of(d->pool_out), view_of(d->pool_add));
+    // K-split scratch, as the forward provides it (runtime.cpp: run)
+    const int64_t mo = (int64_t)a.Nimg * a.Ho * a.Wo * a.Cout;
+    float* part = nullptr;
+    if (d->mode == 1 && mo <= (1 << 20)) {
+      DD_HIP_CHECK(hipMalloc(&part, (size_t)(8 * mo) * sizeof(float)));
+      a.split_part = part;
+      a.split_cap = 8 * mo;
+    }
+    hipError_t e = hipSuccess;
+    try {
+      const ConvRoute r = launch_conv_gemm(a, S(stream));
+      ran(r);
+      d->fused_ln = r.ln;
+      d->fused_pool = r.pooled;
+      e = hipStreamSynchronize(S(stream));  // the split images die with `ar`
+    } catch (...) {
+      if (part) (void)hipFree(part);
+      throw;
+    }
+    if (part) DD_HIP_CHECK(hipFree(part));
+    DD_HIP_CHECK(e);
+  });
+}
+
+int dd_op_layernorm_ld(const float* x, int64_t ldx, const float* res, int64_t ldres, int res_div, const float* g,
+                       const float* b, const float* film_scale, const float* film_shift, int film_div,
+                       int64_t film_ld, float* y, int64_t ldy, int rows, int C, void* stream) {
+  return op_guard([&] {
+    if (!x || !y || !g || !b || rows < 0 || C < 1 || ldx < C || ldy < C)
+      throw std::invalid_argument("dd_op_layernorm_ld: null pointer or a leading dimension below C");
+    launch_layernorm(x, ldx, res, ldres, res_div, g, b, film_scale, film_shift, y, ldy, rows, C, S(stream), film_div,
+                     film_ld);
+  });
+}
+
+int dd_op_bilinear_view(const dd_op_view* in, int B, int Hi, int Wi, int C, const dd_op_view* out, int Ho, int Wo,
+                        int accumulate, void* stream) {
+  return op_guard([&] {
+    if (!in || !out || !in->p || !out->p || B < 1 || Hi < 1 || Wi < 1 || C < 1 || Ho < 1 || Wo < 1)
+      throw std::invalid_argument("dd_op_bilinear_view: null view or bad shape");
+    launch_bilinear(view_of(*in), B, Hi, Wi, C, view_of(*out), Ho, Wo, (float)Hi / (float)Ho, (float)Wi / (float)Wo,
+                    accumulate, S(stream));
+  });
+}
+
 }  // extern "C"

@@ -508,6 +508,50 @@ int dd_op_gpt_attention_rows(const float* qkv, float* y, int B, int T, int C, in
 int dd_op_layernorm_groups(const float* x, const float* g, const float* b, float* y, int groups, int group_rows,
                            long long group_stride, int C, void* stream);
 
+/* ---- the same kernels on strided operand views (test support: the forms the forward launches, which the dense
+ * entries above cannot express) */
+/* (n, h, w, c) view with element strides: element (n, h, w, c) at p + n sn + h sh + w sw + c sc. p null: no operand.
+ * The conv / GEMM operands have sc = 1. Row groups (a GEMM's A, C, res): sn = group stride, sh = row stride, sw = 0. */
+typedef struct dd_op_view {
+  float* p;
+  int64_t sn, sh, sw, sc;
+} dd_op_view;
+/* One conv / GEMM launch, built as the forward builds it (views, then the K slice, the fused LayerNorm, the fused
+ * pooling) and dispatched as dd_op_conv2d_x3 dispatches. A GEMM over G groups of R rows is the 1 x 1 conv with N = G,
+ * H = R, W = 1. */
+typedef struct dd_op_conv_desc {
+  dd_op_view in, out, res; /* res optional, indexed by the output pixel (sn = 0: one image for every n) */
+  int N, H, W, Cin;
+  int KH, KW, stride, pad, Cout;
+  const float* wgt; /* device fp32 [Cout][ldb], K order (kh, kw, ci) */
+  int64_t ldb;      /* floats per weight row; > KH KW Cin only for a K slice */
+  int k0;           /* K slice [k0, k0 + Cin) of the rows (1 x 1 only, k0 % 8 == 0) */
+  const float* bias; /* optional */
+  int relu;
+  int mode; /* 0 = fp32 (conv_gemm), 1 = f16x3, 2 = bf16; 1 / 2 split the weight on the host as dd_create does */
+  unsigned* flags;    /* device word receiving DD_NUM_* bits (modes 1 / 2; nullable) */
+  int64_t route_rows; /* > 0: the dispatcher chooses the tile form for this many rows (a row subset of that GEMM) */
+  float* ln_out; /* optional fused LayerNorm of the output rows (out's row layout), with ln_g / ln_b */
+  const float* ln_g;
+  const float* ln_b;
+  dd_op_view pool_out; /* optional fused pool_p x pool_p mean of the output (+ pool_add, sn ignored: one for all n) */
+  int pool_p;
+  dd_op_view pool_add;
+  int fused_ln;   /* out: 1 if the launch wrote ln_out (otherwise it is untouched) */
+  int fused_pool; /* out: 1 if the launch wrote pool_out (otherwise it is untouched) */
+} dd_op_conv_desc;
+size_t dd_op_conv_desc_size(void);
+/* Synchronous. The route taken is in dd_op_last_kernel. */
+int dd_op_conv_view(dd_op_conv_desc* d, void* stream);
+/* dd_op_layernorm with leading dimensions: row r of x / y at r ldx / r ldy, the residual row r / res_div at ldres;
+ * film_div > 0: the FiLM vectors of row group r / film_div, film_ld floats apart (0: one pair for every row). */
+int dd_op_layernorm_ld(const float* x, int64_t ldx, const float* res, int64_t ldres, int res_div, const float* g,
+                       const float* b, const float* film_scale, const float* film_shift, int film_div,
+                       int64_t film_ld, float* y, int64_t ldy, int rows, int C, void* stream);
+/* dd_op_bilinear / dd_op_bilinear_add (accumulate = 1) on strided views. */
+int dd_op_bilinear_view(const dd_op_view* in, int B, int Hi, int Wi, int C, const dd_op_view* out, int Ho, int Wo,
+                        int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

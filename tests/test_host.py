@@ -102,6 +102,23 @@ def test_library_loads_and_exports_header_symbols():
         assert s in _lib.EXPORTED, f"{s} is not bound in _lib._SIGS"
 
 
+def test_conv_desc_binding_matches_the_library():
+    """dd_op_conv_desc as _lib.py declares it has the size the library compiled, and the fields sit where the header's
+    order puts them (the last field ends the struct up to its alignment)."""
+    import ctypes
+    from diffusiondrive_amd import _lib
+    lib = _lib.load()
+    assert ctypes.sizeof(_lib.DDOpConvDesc) == lib.dd_op_conv_desc_size()
+    assert ctypes.sizeof(_lib.DDOpView) == 40
+    hdr = open(os.path.join(ROOT, "include", "ddmi.h")).read()
+    body = re.search(r"typedef struct dd_op_conv_desc \{(.*?)\} dd_op_conv_desc;", hdr, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    names = [n for decl in body.split(";") for n in re.findall(r"(\w+)\s*(?:,|$)", decl.strip())]
+    assert names == [n.rstrip("_") for n, _ in _lib.DDOpConvDesc._fields_]
+    last = _lib.DDOpConvDesc.fused_pool
+    assert last.offset + last.size <= ctypes.sizeof(_lib.DDOpConvDesc) < last.offset + last.size + 8
+
+
 def test_abi_errors_without_gpu_work():
     """Argument validation runs before any device work and reports through dd_last_error."""
     import ctypes

@@ -28,6 +28,14 @@ def rnd(*shape, seed=0, scale=1.0):
     return torch.randn(*shape, generator=gen) * scale
 
 
+def nans(*shape, device=DEV):
+    """An output buffer: NaN wherever the kernel writes nothing (torch.empty often hands back the previous case's
+    answer from the caching allocator), so an unwritten element fails close()."""
+    if len(shape) == 1 and not isinstance(shape[0], int):
+        shape = tuple(shape[0])
+    return torch.full(shape, float("nan"), device=device)
+
+
 def ok(rc, lib):
     _lib.check(rc, lib, op=True)
     torch.cuda.synchronize()
@@ -61,7 +69,7 @@ def test_conv2d(gpu, B, H, W, Cin, Cout, k, s, p, relu, res):
         ref = ref + r
     if relu:
         ref = F.relu(ref)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     xin, win, bin_ = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1)), g(b)
     rin = g(r.permute(0, 2, 3, 1)) if res else None
     ok(gpu.dd_op_conv2d(xin.data_ptr(), B, H, W, Cin, win.data_ptr(), bin_.data_ptr(),
@@ -89,7 +97,7 @@ def test_conv2d(gpu, B, H, W, Cin, Cout, k, s, p, relu, res):
     (3, 90, 250, 64, 256, 3, 2, 1, False, False), # stride 2, ragged M
     (1, 128, 128, 64, 512, 1, 1, 0, True, True),  # 256 x 128 tiles (3 stages) for Cout > 128
     (1, 64, 128, 128, 512, 1, 1, 0, False, True), # 128 x 128 tiles (4 waves, 3 stages)
-    (1, 70, 130, 160, 400, 1, 1, 0, False, True), # 128 x 128 tiles, ragged M and N
+    (1, 70, 130, 160, 400, 1, 1, 0, False, True), # ragged M and N; too few tiles for conv_x5: conv_x3 64 x 64
     (1, 64, 128, 132, 512, 1, 1, 0, True, False), # 128 x 128 tiles, generic K (Cin % 32 != 0)
     (1, 256, 256, 64, 256, 3, 2, 1, True, False), # 128 x 128 tiles, 3x3 stride-2 tap walk
     (4, 130, 126, 64, 128, 1, 2, 0, False, False),# 1x1 stride-2 downsample, 128 x 128 two per CU, ragged M
@@ -112,7 +120,7 @@ def test_conv2d_f16x3(gpu, B, H, W, Cin, Cout, k, s, p, relu, res):
         ref = ref + r.double()
     if relu:
         ref = F.relu(ref)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win, bin_ = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1)), g(b)
     rin = g(r.permute(0, 2, 3, 1)) if res else None
@@ -122,6 +130,7 @@ def test_conv2d_f16x3(gpu, B, H, W, Cin, Cout, k, s, p, relu, res):
     close(out.permute(0, 3, 1, 2), ref, 3e-5)
     assert int(flags.item()) == 0
     # bf16 (reduced precision, one product): same kernel family, bf16-rounding tolerance
+    out.fill_(float("nan"))  # not the f16x3 result, which would pass the bar below untouched
     ok(gpu.dd_op_conv2d_x3(xin.data_ptr(), B, H, W, Cin, win.data_ptr(), bin_.data_ptr(),
                            rin.data_ptr() if res else None, out.data_ptr(), Cout, k, k, s, p, int(relu), 1,
                            flags.data_ptr(), None), gpu)
@@ -155,7 +164,7 @@ def test_conv2d_f16x3_b64_routes(gpu, B, H, W, Cin, Cout, k, s, p, relu, res, ro
         ref = ref + r.double()
     if relu:
         ref = F.relu(ref)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win, bin_ = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1)), g(b)
     rin = g(r.permute(0, 2, 3, 1)) if res else None
@@ -190,7 +199,7 @@ def test_conv2d_small_grid_form_is_bit_identical(gpu, monkeypatch, B, H, W, Cin,
 
     def run(small):
         monkeypatch.setenv("DDMI_X6_SMALL", small)
-        out = torch.empty(B, H, W, Cout, device=DEV)
+        out = nans(B, H, W, Cout, device=DEV)
         flags = torch.zeros(1, dtype=torch.int32, device=DEV)
         ok(gpu.dd_op_conv2d_x3(xin.data_ptr(), B, H, W, Cin, win.data_ptr(), bin_.data_ptr(), rin.data_ptr(),
                                out.data_ptr(), Cout, 3, 3, 1, 1, 1, prec, flags.data_ptr(), None), gpu)
@@ -274,7 +283,7 @@ def test_conv2d_bf16(gpu, B, H, W, Cin, Cout, k, s, p, res, route):
     ref_b = F.relu(F.conv2d(x.to(torch.bfloat16).double(), w.to(torch.bfloat16).double(), b.double(), s, p)
                    + (r.double() if res else 0))
     ref = F.relu(ref0 + (r.double() if res else 0))
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win, bin_ = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1)), g(b)
     rin = g(r.permute(0, 2, 3, 1)) if res else None
@@ -295,7 +304,7 @@ def test_stem_pool_bf16(gpu, B, H, W):
     b = rnd(64, seed=83)
     xb, wb = x.to(torch.bfloat16).double(), w.to(torch.bfloat16).double()
     ref = F.max_pool2d(F.relu(F.conv2d(xb, wb, b.double(), 2, 3)), 3, 2, 1)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win, bin_ = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1)), g(b)
     ok(gpu.dd_op_stem_pool(xin.data_ptr(), B, H, W, win.data_ptr(), bin_.data_ptr(), out.data_ptr(), 1,
@@ -320,7 +329,7 @@ def test_stem_pool_nchw(gpu, monkeypatch, B, C, H, W, prec, one):
     b = rnd(64, seed=87)
     xr, wr = (x.to(torch.bfloat16).double(), w.to(torch.bfloat16).double()) if prec else (x.double(), w.double())
     ref = F.max_pool2d(F.relu(F.conv2d(xr, wr[:, :C], b.double(), 2, 3)), 3, 2, 1)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win, bin_ = g(x), g(w.permute(0, 2, 3, 1)), g(b)
     ok(gpu.dd_op_stem_pool_nchw(xin.data_ptr(), B, C, H, W, win.data_ptr(), bin_.data_ptr(), out.data_ptr(), prec,
@@ -339,7 +348,7 @@ def test_conv2d_f16x3_small_activations(gpu, scale):
     x = rnd(B, Cin, H, W, seed=41).abs() * scale
     w = rnd(Cout, Cin, 3, 3, seed=42, scale=1.0 / np.sqrt(Cin * 9))
     ref = F.conv2d(x.double(), w.double(), None, 1, 1)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1))
     ok(gpu.dd_op_conv2d_x3(xin.data_ptr(), B, H, W, Cin, win.data_ptr(), None, None, out.data_ptr(), Cout, 3, 3, 1,
@@ -357,7 +366,7 @@ def test_conv2d_f16x3_flags_overflow(gpu):
     x = rnd(1, 32, 8, 8, seed=15)
     x[0, 3, 2, 2] = 1e6
     w = rnd(32, 32, 1, 1, seed=16)
-    out = torch.empty(1, 8, 8, 32, device=DEV)
+    out = nans(1, 8, 8, 32, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1))
     ok(gpu.dd_op_conv2d_x3(xin.data_ptr(), 1, 8, 8, 32, win.data_ptr(), None, None, out.data_ptr(), 32, 1, 1, 1, 0,
@@ -370,7 +379,7 @@ def test_conv2d_x6_flags_overflow(gpu):
     x = rnd(1, 32, 16, 16, seed=15)
     x[0, 5, 7, 9] = 1e6
     w = rnd(64, 32, 3, 3, seed=16)
-    out = torch.empty(1, 16, 16, 64, device=DEV)
+    out = nans(1, 16, 16, 64, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1))
     ok(gpu.dd_op_conv2d_x3(xin.data_ptr(), 1, 16, 16, 32, win.data_ptr(), None, None, out.data_ptr(), 64, 3, 3, 1,
@@ -389,7 +398,7 @@ def test_gemm(gpu, M, K, N, relu):
     ref = a @ w.T + b + r
     if relu:
         ref = F.relu(ref)
-    out = torch.empty(M, N, device=DEV)
+    out = nans(M, N, device=DEV)
     ad, wd, bd, rd = g(a), g(w), g(b), g(r)
     ok(gpu.dd_op_gemm(ad.data_ptr(), M, K, wd.data_ptr(), bd.data_ptr(), rd.data_ptr(), out.data_ptr(), N,
                       int(relu), None), gpu)
@@ -402,7 +411,7 @@ def test_gemm_batched(gpu, batch, M, N, K, kn):
     a = rnd(batch, M, K, seed=9)
     bm = rnd(batch, K, N, seed=10) if kn else rnd(batch, N, K, seed=10)
     ref = a @ (bm if kn else bm.transpose(1, 2))
-    out = torch.empty(batch, M, N, device=DEV)
+    out = nans(batch, M, N, device=DEV)
     ad, bd = g(a), g(bm)
     ok(gpu.dd_op_gemm_batched(ad.data_ptr(), bd.data_ptr(), out.data_ptr(), batch, M, N, K, kn, None), gpu)
     close(out, ref, 2e-5)
@@ -420,7 +429,7 @@ def test_layernorm(gpu, rows, C, res_div, film):
     ref = F.layer_norm(xin, (C,), gam, bet, 1e-5)
     if film:
         ref = ref * (1 + fs) + fb
-    out = torch.empty(rows, C, device=DEV)
+    out = nans(rows, C, device=DEV)
     keep = [g(t) if t is not None else None for t in (x, res, gam, bet, fs, fb)]
     p = [t.data_ptr() if t is not None else None for t in keep]
     ok(gpu.dd_op_layernorm(p[0], p[1], max(res_div, 1), p[2], p[3], p[4], p[5], out.data_ptr(), rows, C, None), gpu)
@@ -440,7 +449,7 @@ def test_softmax(gpu):
 def test_bilinear(gpu, B, Hi, Wi, C, Ho, Wo):
     x = rnd(B, C, Hi, Wi, seed=18)
     ref = F.interpolate(x, size=(Ho, Wo), mode="bilinear", align_corners=False)
-    out = torch.empty(B, Ho, Wo, C, device=DEV)
+    out = nans(B, Ho, Wo, C, device=DEV)
     xd = g(x.permute(0, 2, 3, 1))
     ok(gpu.dd_op_bilinear(xd.data_ptr(), B, Hi, Wi, C, out.data_ptr(), Ho, Wo, None), gpu)
     close(out.permute(0, 3, 1, 2), ref, 1e-6)
@@ -463,7 +472,7 @@ def test_bilinear_add(gpu, B, Hi, Wi, C, Ho, Wo):
 def test_maxpool(gpu):
     x = rnd(2, 64, 37, 50, seed=19)
     ref = F.max_pool2d(x, 3, 2, 1)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     xd = g(x.permute(0, 2, 3, 1))
     ok(gpu.dd_op_maxpool3x3s2(xd.data_ptr(), 2, 37, 50, 64, out.data_ptr(), None), gpu)
     close(out.permute(0, 3, 1, 2), ref, 0.0)
@@ -473,7 +482,7 @@ def test_maxpool(gpu):
 def test_avgpool(gpu, H, W, oh, ow):
     x = rnd(2, 64, H, W, seed=20)
     ref = F.adaptive_avg_pool2d(x, (oh, ow))
-    out = torch.empty(2, oh, ow, 64, device=DEV)
+    out = nans(2, oh, ow, 64, device=DEV)
     xd = g(x.permute(0, 2, 3, 1))
     ok(gpu.dd_op_avgpool(xd.data_ptr(), 2, H, W, 64, oh, ow, out.data_ptr(), None), gpu)
     close(out.permute(0, 3, 1, 2), ref, 1e-6)
@@ -489,7 +498,7 @@ def test_bev_sample_attn(gpu):
     grid = torch.stack([pts[..., 1] / 32.0, pts[..., 0] / 32.0], -1)
     s = F.grid_sample(value, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
     ref = (torch.softmax(logits, -1).unsqueeze(1) * s).sum(-1).permute(0, 2, 1)
-    out = torch.empty(B, Q, C, device=DEV)
+    out = nans(B, Q, C, device=DEV)
     ld, pd, vd = g(logits), g(pts), g(value.permute(0, 2, 3, 1))
     ok(gpu.dd_op_bev_sample_attn(ld.data_ptr(), pd.data_ptr(), vd.data_ptr(), out.data_ptr(), B, Q, P, H, W, C,
                                  None), gpu)
@@ -522,7 +531,7 @@ def test_mha_small(gpu, B, nh, hd, Lq, Lk):
     kh = k.double().view(B, Lk, nh, hd).transpose(1, 2)
     vh = v.double().view(B, Lk, nh, hd).transpose(1, 2)
     ref = (torch.softmax(qh @ kh.transpose(-1, -2) / np.sqrt(hd), -1) @ vh).transpose(1, 2).reshape(B, Lq, nh * hd)
-    out = torch.empty(B, Lq, nh * hd, device=DEV)
+    out = nans(B, Lq, nh * hd, device=DEV)
     qd, kd, vd = g(q), g(k), g(v)
     ok(gpu.dd_op_mha_small(qd.data_ptr(), kd.data_ptr(), vd.data_ptr(), out.data_ptr(), B, Lq, Lk, nh, hd, None), gpu)
     close(out, ref, 1e-5)
@@ -538,7 +547,7 @@ def test_gpt_attention(gpu, B, T, C):
     q, k, v = (t.reshape(B, T, nh, hs).transpose(1, 2) for t in qkv.split(C, -1))
     att = torch.softmax((q @ k.transpose(-2, -1)) * (1.0 / np.sqrt(hs)), -1)
     ref = (att @ v).transpose(1, 2).reshape(B, T, C)
-    out = torch.empty(B, T, C, device=DEV)
+    out = nans(B, T, C, device=DEV)
     qd = g(qkv)
     ok(gpu.dd_op_gpt_attention(qd.data_ptr(), out.data_ptr(), B, T, C, nh, 0, None), gpu)
     close(out, ref, 2e-5)
@@ -559,7 +568,7 @@ def test_gpt_attention_f16x3(gpu, B, T, C, amp, prec):
     q, k, v = (t.double().reshape(B, T, nh, hs).transpose(1, 2) for t in qkv.split(C, -1))
     att = torch.softmax((q @ k.transpose(-2, -1)) * (1.0 / np.sqrt(hs)), -1)
     ref = (att @ v).transpose(1, 2).reshape(B, T, C)
-    out = torch.empty(B, T, C, device=DEV)
+    out = nans(B, T, C, device=DEV)
     qd = g(qkv)
     ok(gpu.dd_op_gpt_attention(qd.data_ptr(), out.data_ptr(), B, T, C, nh, prec, None), gpu)
     close(out, ref, 2e-5)
@@ -573,7 +582,7 @@ def test_stem_pool_f16x3(gpu, B, H, W):
     w = rnd(64, 4, 7, 7, seed=42, scale=1.0 / np.sqrt(196))
     b = rnd(64, seed=43)
     ref = F.max_pool2d(F.relu(F.conv2d(x.double(), w.double(), b.double(), 2, 3)), 3, 2, 1)
-    out = torch.empty(ref.permute(0, 2, 3, 1).shape, device=DEV)
+    out = nans(ref.permute(0, 2, 3, 1).shape, device=DEV)
     flags = torch.zeros(1, dtype=torch.int32, device=DEV)
     xin, win, bin_ = g(x.permute(0, 2, 3, 1)), g(w.permute(0, 2, 3, 1)), g(b)
     ok(gpu.dd_op_stem_pool_x3(xin.data_ptr(), B, H, W, win.data_ptr(), bin_.data_ptr(), out.data_ptr(),
@@ -590,7 +599,7 @@ def test_mk_linear_core(gpu, K, N):
     w = rnd(N, K, seed=92, scale=1.0 / np.sqrt(K))
     b = rnd(N, seed=93)
     ref = a.double() @ w.double().T + b.double()
-    out = torch.empty(32, N, device=DEV)
+    out = nans(32, N, device=DEV)
     ad, wd, bd = g(a), g(w), g(b)
     ok(gpu.dd_op_mk_linear(ad.data_ptr(), K, wd.data_ptr(), bd.data_ptr(), out.data_ptr(), N, None), gpu)
     close(out, ref, 3e-5)
@@ -611,7 +620,7 @@ def test_bevproj_fused(gpu, B):
     bil = F.interpolate(kvp.double().permute(0, 3, 1, 2), size=(H, W), mode="bilinear", align_corners=False)
     v = F.relu(p3.double() @ w.double().T + bias.double() + bil.permute(0, 2, 3, 1).reshape(-1, 256))
     ref = F.layer_norm(v, (256,), lg.double(), lb.double(), 1e-5)
-    out = torch.empty(B * H * W, 256, device=DEV)
+    out = nans(B * H * W, 256, device=DEV)
     cd, kd, wd, bd, gd, ld = g(cat), g(kvp), g(w), g(bias), g(lg), g(lb)
     ok(gpu.dd_op_bevproj(cd.data_ptr() + 256 * 4, 320, kd.data_ptr(), wd.data_ptr(), bd.data_ptr(), gd.data_ptr(),
                          ld.data_ptr(), out.data_ptr(), B, H, W, 8, 8, None), gpu)
