@@ -83,6 +83,25 @@ class DDComfortParams(ctypes.Structure):
     ]
 
 
+class DDAreaParams(ctypes.Structure):
+    """dd_area_params: the vehicle's lever arms, dt and the driving-direction constants of dd_ego_areas
+    (include/ddmi.h)."""
+    _fields_ = [
+        ("half_length", ctypes.c_double), ("half_width", ctypes.c_double), ("rear_axle_to_center", ctypes.c_double),
+        ("dt", ctypes.c_double), ("driving_direction_horizon", ctypes.c_double),
+        ("driving_direction_compliance_threshold", ctypes.c_double),
+        ("driving_direction_violation_threshold", ctypes.c_double),
+    ]
+
+
+class DDDrivableMaps(ctypes.Structure):
+    """dd_drivable_maps: the map polygons of G scenes as flat device arrays (include/ddmi.h)."""
+    _fields_ = [
+        ("verts", c_void_p), ("ring_off", c_void_p), ("poly_ring_off", c_void_p), ("poly_kind", c_void_p),
+        ("scene_poly_off", c_void_p), ("num_polys", ctypes.c_int),
+    ]
+
+
 class DDOpView(ctypes.Structure):
     """dd_op_view: a strided (n, h, w, c) operand of the view-taking single-op entries (include/ddmi.h)."""
     _fields_ = [("p", c_void_p), ("sn", ctypes.c_int64), ("sh", ctypes.c_int64), ("sw", ctypes.c_int64),
@@ -152,6 +171,11 @@ _SIGS = {
     "dd_default_comfort_params": (None, [ctypes.POINTER(DDComfortParams)]),
     "dd_comfort": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.POINTER(DDComfortParams), c_void_p, c_void_p,
                                   c_void_p]),
+    "dd_default_area_params": (None, [ctypes.POINTER(DDAreaParams)]),
+    "dd_ego_areas_work": (ctypes.c_size_t, [ctypes.c_int]),
+    "dd_ego_areas": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDDrivableMaps), ctypes.c_int,
+                                    ctypes.POINTER(DDAreaParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
     "dd_set_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_set_schedule": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_get_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int)]),

@@ -198,6 +198,18 @@ class DiffusionDriveAgent(_Base):
             states = states.to(torch.device("cuda", self._transfuser_model.device))
         return comfort_metrics(states, params, signals)
 
+    def ego_areas(self, states: torch.Tensor, maps, params=None, coords: bool = False):
+        """The map flags of the PDM score on the GPU (``diffusiondrive_amd.simulate.ego_areas``): per state whether the
+        vehicle is in multiple lanes, in non-drivable area, in oncoming traffic (``PDMScorer._calculate_ego_area``,
+        pdm_scorer.py:240-291), and the drivable-area and driving-direction compliance scores (:351-396) of every
+        candidate of the (B, ..., 41, 11) float64 states ``simulate_trajectories`` returns, on the B scenes' maps
+        (``pack_drivable_maps``' result, or what it takes). A host tensor is moved to the model's device."""
+        from .simulate import ego_areas
+        states = torch.as_tensor(states)
+        if states.device.type != "cuda":
+            states = states.to(torch.device("cuda", self._transfuser_model.device))
+        return ego_areas(states, maps, params, coords)
+
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).
 TransfuserAgent = DiffusionDriveAgent

@@ -19,6 +19,8 @@
 
 struct dd_sim_params;  // include/ddmi.h
 struct dd_comfort_params;
+struct dd_area_params;
+struct dd_drivable_maps;
 
 namespace ddmi {
 
@@ -624,5 +626,13 @@ void launch_simulate(const float* traj, const double* proposals, const double* e
 // or null. One launch; the parameters are checked by the caller.
 void launch_comfort(const double* states, int N, const dd_comfort_params& p, uint8_t* out_flags, double* out_signals,
                     hipStream_t st);
+
+// ---- ego_areas.hip: PDM map compliance (dd_ego_areas) of (N, 41, 11) states against the maps of G = N / per_group
+// scenes; work = ego_areas_work_doubles(P) doubles (the polygons' bounding boxes, filled by the first of the two
+// launches); horizon = int(driving_direction_horizon / dt), 0..40. The parameters are checked by the caller.
+size_t ego_areas_work_doubles(int P);
+void launch_ego_areas(const double* states, int N, int per_group, const dd_drivable_maps& maps, int G,
+                      const dd_area_params& p, int horizon, double* work, uint8_t* out_areas, double* out_scores,
+                      double* out_progress, double* out_coords, hipStream_t st);
 
 }  // namespace ddmi

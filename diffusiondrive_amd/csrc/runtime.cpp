@@ -2681,6 +2681,76 @@ int dd_comfort(const double* states, int N, const dd_comfort_params* p, uint8_t*
   });
 }
 
+// ---- map compliance (ego_areas.hip): stateless, every argument checked before any device work
+void dd_default_area_params(dd_area_params* p) {
+  if (!p) return;
+  // nuPlan's VehicleParameters, from get_pacifica_parameters' front length, rear length and width (ddmi.h)
+  const double front_length = 4.049, rear_length = 1.127, width = 2.297;
+  const double length = front_length + rear_length;
+  p->half_length = length / 2.0;
+  p->half_width = width / 2.0;
+  p->rear_axle_to_center = std::fabs(length / 2.0 - rear_length);
+  p->dt = 0.1;
+  p->driving_direction_horizon = 1.0;
+  p->driving_direction_compliance_threshold = 2.0;
+  p->driving_direction_violation_threshold = 6.0;
+}
+
+size_t dd_ego_areas_work(int P) { return ddmi::ego_areas_work_doubles(P); }
+
+int dd_ego_areas(const double* states, int N, int per_group, const dd_drivable_maps* maps, int G,
+                 const dd_area_params* p, double* work, uint8_t* out_areas, double* out_scores, double* out_progress,
+                 double* out_coords, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_ego_areas: " + what); };
+    if (N <= 0) bad("N = " + std::to_string(N) + " must be positive");
+    if (per_group <= 0) bad("per_group = " + std::to_string(per_group) + " must be positive");
+    if (N % per_group) bad("N = " + std::to_string(N) + " is not a multiple of per_group = " + std::to_string(per_group));
+    if (G != N / per_group)
+      bad("G = " + std::to_string(G) + " is not N / per_group = " + std::to_string(N / per_group));
+    if (!states) bad("states is null");
+    if (!maps) bad("maps is null");
+    if (!p) bad("params is null");
+    if (!work) bad("work is null");
+    if (!out_areas) bad("out_areas is null");
+    if (!out_scores) bad("out_scores is null");
+    if (!maps->scene_poly_off) bad("dd_drivable_maps.scene_poly_off is null");
+    if (maps->num_polys < 0) bad("dd_drivable_maps.num_polys = " + std::to_string(maps->num_polys) + " is negative");
+    if (maps->num_polys > 0) {
+      if (!maps->verts) bad("dd_drivable_maps.verts is null");
+      if (!maps->ring_off) bad("dd_drivable_maps.ring_off is null");
+      if (!maps->poly_ring_off) bad("dd_drivable_maps.poly_ring_off is null");
+      if (!maps->poly_kind) bad("dd_drivable_maps.poly_kind is null");
+    }
+    auto positive = [&](const char* field, double v) {
+      if (!(v > 0.0) || !std::isfinite(v))
+        bad(std::string("dd_area_params.") + field + " = " + std::to_string(v) + " must be positive and finite");
+    };
+    positive("half_length", p->half_length);
+    positive("half_width", p->half_width);
+    positive("rear_axle_to_center", p->rear_axle_to_center);
+    positive("dt", p->dt);
+    auto threshold = [&](const char* field, double v) {
+      if (std::isnan(v) || v < 0.0)
+        bad(std::string("dd_area_params.") + field + " = " + std::to_string(v) + " must not be NaN or negative");
+    };
+    threshold("driving_direction_compliance_threshold", p->driving_direction_compliance_threshold);
+    threshold("driving_direction_violation_threshold", p->driving_direction_violation_threshold);
+    if (p->driving_direction_compliance_threshold > p->driving_direction_violation_threshold)
+      bad("dd_area_params.driving_direction_compliance_threshold = " +
+          std::to_string(p->driving_direction_compliance_threshold) +
+          " is above driving_direction_violation_threshold = " +
+          std::to_string(p->driving_direction_violation_threshold));
+    // int(horizon / dt) as Python forms it: the quotient truncated towards zero
+    const double steps = std::trunc(p->driving_direction_horizon / p->dt);
+    if (!(steps >= 0.0 && steps <= 40.0))
+      bad("dd_area_params.driving_direction_horizon = " + std::to_string(p->driving_direction_horizon) +
+          ": int(horizon / dt) must be in [0, 40]");
+    ddmi::launch_ego_areas(states, N, per_group, *maps, G, *p, (int)steps, work, out_areas, out_scores, out_progress,
+                           out_coords, static_cast<hipStream_t>(stream));
+  });
+}
+
 int dd_set_profiling(dd_handle* h, int enable) {
   return guarded([&] {
     if (!h) throw std::invalid_argument("null handle");

@@ -29,6 +29,9 @@
  *                  then the same simulation
  *   dd_comfort   <- ego_is_comfortable                          pdm_planner/scoring/pdm_comfort_metrics.py:313-336
  *                  (the six comfort flags of the simulated states, and optionally the six filtered signals)
+ *   dd_ego_areas <- PDMScorer._calculate_ego_area, _calculate_drivable_area_compliance and
+ *                  _calculate_driving_direction_compliance      pdm_planner/scoring/pdm_scorer.py:240-291,351-396
+ *                  (the three map flags of every simulated state and the two scores that need nothing else)
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
  * handle must be serialised by the caller (the reference runs one agent per worker process,
@@ -303,8 +306,9 @@ int dd_tap(dd_handle* h, const char* name, float* dst, size_t count, size_t* act
  * model for 40 steps - and computes every sub-score from the simulated states. These entries run that simulation for N
  * candidates (dd_forward_samples draws up to 32 x 20 per scene) without a handle, in float64 throughout as the
  * reference does, deterministically (no atomics; two calls on the same input are bit-equal). Of the sub-scores, comfort
- * is in scope (dd_comfort below: it needs nothing but the states); the others (collision, drivable area, progress, TTC)
- * need the map and the observations and are out of scope. */
+ * is in scope (dd_comfort below: it needs nothing but the states), and so are drivable-area and driving-direction
+ * compliance (dd_ego_areas below: the states and the scene's map polygons); collision, progress and TTC need the
+ * observations and the centerline as well and are out of scope. */
 typedef struct dd_sim_params {
   double wheel_base;                /* 3.089 m (nuPlan's get_pacifica_parameters) */
   double dt;                        /* 0.1 s: the proposal's sampling interval and the tracker's discretisation; the
@@ -392,6 +396,80 @@ void dd_default_comfort_params(dd_comfort_params* p);
  * its upper bound when both are non-zero (a negative symmetric bound, or min_lon_accel >= max_lon_accel). */
 int dd_comfort(const double* states, int N, const dd_comfort_params* params, uint8_t* out_flags, double* out_signals,
                void* stream);
+
+/* ---- map compliance of simulated states (PDMScorer._calculate_ego_area, pdm_scorer.py:240-291, and the two scores
+ * taken from it alone: drivable-area compliance :351-358 and driving-direction compliance :360-396, on the GPU) ---- */
+/* The vehicle figures are formed in double the way nuPlan's VehicleParameters forms them from get_pacifica_parameters'
+ * front length 4.049, rear length 1.127 and width 2.297: length = front + rear, half_length = length / 2, half_width =
+ * width / 2, rear_axle_to_center = |length / 2 - rear|. Those three figures, like dd_sim_params.wheel_base, are quoted
+ * from memory of nuPlan, which is not part of this tree: they are parameters so that a caller who holds the real
+ * VehicleParameters passes its own. */
+typedef struct dd_area_params {
+  double half_length;          /* 2.588 m */
+  double half_width;           /* 1.1485 m */
+  double rear_axle_to_center;  /* 1.461 m */
+  double dt;                   /* 0.1 s between states (proposal_sampling.interval_length) */
+  double driving_direction_horizon;               /* 1.0 s; the window holds int(horizon / dt) + 1 samples */
+  double driving_direction_compliance_threshold;  /* 2.0 m: below it the driving-direction score is 1 */
+  double driving_direction_violation_threshold;   /* 6.0 m: below it 0.5, else 0 */
+} dd_area_params;
+/* Fill *p with the values listed above. */
+void dd_default_area_params(dd_area_params* p);
+/* The drivable-area maps of G scenes as flat device arrays. A ring is a run of vertices whose closing edge, last to
+ * first, is implied; a repeated closing vertex (as shapely stores it) is a harmless zero-length edge. A polygon is one
+ * or more rings under the even-odd rule (the exterior first, then the holes: any order gives the same answer). The
+ * rings of a polygon, the polygons of a scene and the scenes follow each other in the arrays. The offset arrays are
+ * read on the device and are TRUSTED, not validated: every offset array must start at 0 and never decrease, ring_off
+ * must end at the vertex count, poly_ring_off at the ring count, scene_poly_off at num_polys, and every ring must
+ * have at least 3 vertices, all finite. diffusiondrive_amd.simulate.pack_drivable_maps guarantees that. */
+typedef struct dd_drivable_maps {
+  const double* verts;            /* device double (V, 2): x, y */
+  const int32_t* ring_off;        /* device int32 (R + 1): ring r = vertices ring_off[r] .. ring_off[r + 1] - 1 */
+  const int32_t* poly_ring_off;   /* device int32 (P + 1): polygon p = rings poly_ring_off[p] .. poly_ring_off[p+1]-1 */
+  const uint8_t* poly_kind;       /* device uint8 (P): bit 0 lane class (LANE, LANE_CONNECTOR); bit 1 drivable class
+                                     (ROADBLOCK, INTERSECTION, DRIVABLE_AREA, CARPARK_AREA); bit 2 on route (the
+                                     polygon's token is in route_lane_ids), read only together with bit 0 */
+  const int32_t* scene_poly_off;  /* device int32 (G + 1): scene g = polygons scene_poly_off[g] .. [g + 1] - 1; a scene
+                                     may have none */
+  int num_polys;                  /* P, the host's copy of scene_poly_off[G]; with P = 0 the first four may be NULL */
+} dd_drivable_maps;
+/* Device scratch of one call over maps of P polygons, in doubles: the closed bounding box of every polygon, which the
+ * call's first small launch fills. Never 0, so that the scratch pointer of an all-empty map is still a pointer. */
+size_t dd_ego_areas_work(int P);
+/* states: device double (N, 41, 11) in StateIndex order, exactly what dd_simulate / dd_simulate_proposals write, read
+ * in place (x, y, heading = columns 0..2, the rear-axle pose). Candidate n is scored on the map of scene n / per_group,
+ * as in dd_simulate; G must be N / per_group. Per state the five points of state_array_to_coords_array
+ * (pdm_array_representation.py:142-181) in BBCoordsIndex order - front-left, rear-left, rear-right, front-right,
+ * center; center = (x, y) + rear_axle_to_center (cos h, sin h), corner = center + (lat cos(h + pi/2) + lon cos h,
+ * lat sin(h + pi/2) + lon sin h) with the cosine of the rounded sum, as translate_lon_and_lat forms it - are tested
+ * against every polygon of the scene. A point is in a polygon when it lies in its interior (shapely's contains): a
+ * point on an edge or a vertex is outside, a point in a hole is outside; a point with a NaN coordinate is outside
+ * everything. The test is a crossing count over coordinate differences (no product of absolute coordinates), exact on
+ * an edge wherever the two products are exact and otherwise right for every point further from an edge than the
+ * rounding of one product of two differences.
+ *   out_areas: device uint8 (N, 41, 3) in EgoAreaIndex order:
+ *     0 multiple lanes  more than one lane-class polygon holds at least one corner and none holds all four
+ *     1 non-drivable    fewer than four corners lie in the union of the drivable-class polygons (per corner: the four
+ *                       may lie in four polygons; lane-class polygons do not count)
+ *     2 oncoming        the CENTER (not the rear axle) is in no lane-class polygon that is on route
+ *   out_scores: device double (N, 2): [drivable-area compliance: 0 if any state is non-drivable, else 1;
+ *     driving-direction compliance: 1 if m < compliance_threshold, 0.5 if m < violation_threshold, else 0 (a NaN m
+ *     gives 0)], m = max_t sum(p[max(0, t - h) .. t]), h = int(horizon / dt) (eleven samples by default), p[0] = 0,
+ *     p[t] = |center[t] - center[t - 1]| where the oncoming flag AT t is set, else 0
+ *   out_progress: device double (N) or NULL: m
+ *   out_coords: device double (N, 41, 5, 2) or NULL: the five points
+ * With an empty map every state is non-drivable and oncoming and never in multiple lanes. Two launches on `stream`
+ * (the bounding boxes, then the scoring: one candidate per wavefront, a polygon skipped where none of its points lies
+ * in the polygon's closed bounding box); the call allocates nothing, copies nothing, does not synchronise and uses no
+ * atomics: two calls on the same input are bit-equal. DD_ERR_INVALID before any device work, with the argument or
+ * field named in dd_last_error(): N <= 0, per_group <= 0, N % per_group != 0, G != N / per_group, null states / maps /
+ * params / work / out_areas / out_scores / maps->scene_poly_off, maps->num_polys < 0 or a null map array with
+ * num_polys > 0, a length or dt that is not positive and finite, a threshold that is NaN or negative,
+ * compliance_threshold > violation_threshold, a NaN horizon or int(horizon / dt) (truncated towards zero, as Python's
+ * int) outside 0..40. */
+int dd_ego_areas(const double* states, int N, int per_group, const dd_drivable_maps* maps, int G,
+                 const dd_area_params* params, double* work, uint8_t* out_areas, double* out_scores,
+                 double* out_progress, double* out_coords, void* stream);
 
 /* ---- input feature builder (TransfuserFeatureBuilder.compute_features on the GPU) ---------- */
 /* Camera feature (transfuser_features.py:57-77): crop + stitch + cv2 INTER_LINEAR resize +
