@@ -184,6 +184,7 @@ _SIGS = {
                               ctypes.POINTER(ctypes.c_size_t), c_void_p]),
     "dd_op_last_error": (ctypes.c_char_p, []),
     "dd_op_last_kernel": (ctypes.c_char_p, []),
+    "dd_op_last_walk": (ctypes.c_char_p, []),
     "dd_op_split_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            ctypes.POINTER(ctypes.c_int)]),
     "dd_op_pack_mk_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p]),

@@ -97,6 +97,13 @@ struct ConvArgs {
   int64_t ldh = 0;
   unsigned* flags = nullptr;
   int prec = 0;  // 0 = f16x3 (wh / wl fp16 hi / lo), 1 = bf16 (wh = bf16 image, one product)
+  // Second f16x3 image of a 3x3 / stride 1 / pad 1 conv, for conv_x6's Winograd F(2,3) walk along W
+  // (weights.cpp prep_split_walk): the taps transformed along kx into four planes, hi / lo [Cout][ldh2] fp16
+  // in K order (ky, xi, ci), K = 12 Cin, with their own per-channel inverse scales. Null: no walk.
+  const uint16_t* wh2 = nullptr;
+  const uint16_t* wl2 = nullptr;
+  const float* wsinv2 = nullptr;
+  int64_t ldh2 = 0;
   // Gathered output rows (conv_x3 MODE 1 only): output row m (launch geometry Nimg = 1, Ho = M,
   // Wo = 1, compact rows out + m * out_sh) is the conv at input-geometry pixel rowmap[m] =
   // n * H * W + oh * W + ow (stride 1, Ho = H, Wo = W), or a don't-care row when rowmap[m] < 0.
@@ -405,6 +412,8 @@ struct ConvRoute {
   // kernel + tile configuration, e.g. "conv_x6<8,32,128,4,2>" (TH, TW, BN, wave grid), "conv_x5<256,256>",
   // "conv_x3<128,128,f16x3>"; "" when nothing was launched
   const char* config = "";
+  // K walk other than the direct one: "f23" (conv_x6's Winograd F(2,3) walk along W), "" otherwise
+  const char* walk = "";
   bool pooled = false;  // the launch also wrote ConvArgs::pool_out
   bool ln = false;      // the launch also wrote ConvArgs::ln_out
 };

@@ -114,11 +114,11 @@ __device__ inline uint2 to_bf16x4(const x6f4 v) {  // RNE (v_cvt_pk_bf16_f32)
 // Does a halo issue (at tap TA of some chunk) fall in the D steps before step t, i.e. after the B
 // DMAs of step t were issued (D steps earlier, ahead of that step's halo)? For the first chunk the
 // window stops at step 0 (the prologue issued chunk 0's halo before every B DMA).
-constexpr bool halo_in_window(int t, int D, int TA, bool first) {
+constexpr bool halo_in_window(int t, int D, int TA, bool first, int S = 9) {  // S: steps per chunk
   for (int j = 1; j <= D; ++j) {
     const int u = t - j;
     if (first && u < 0) return false;
-    if (((u % 9) + 9) % 9 == TA) return true;
+    if (((u % S) + S) % S == TA) return true;
   }
   return false;
 }
@@ -148,17 +148,40 @@ extern "C" int dd_x6_stamps_read(unsigned long long* h, int n) {
 // PREC 0: f16x3 (32-channel chunks; a halo pixel row / B slot holds the hi and lo fp16 images of them);
 // PREC 1: bf16 (64-channel chunks; the same bytes hold channels 0-31 and 32-63 of the chunk in bf16, and
 // each fragment set feeds two bf16 MFMAs, ah*bh + al*bl, instead of three f16 ones - one product per MAC).
-template <int TH, int TW, int BN, int WM, int WN, int D, int NSLOT, int SH, int PREC>
+//
+// WALK 1 (f16x3, 8 waves): the Winograd F(2,3) walk along W. The GEMM rows are the BM / 2 output pairs (2p, 2p + 1)
+// of the tile; a chunk's 9 tap steps become 12 steps (ky, xi) of half the MFMAs each, 2/3 of the products:
+//  * A: for the pair p of a halo row, with d_i = in[2p - 1 + i], the staging computes in fp32, before the hi / lo
+//    split, V0 = d0 - d2, V1 = d1 + d2, V2 = d2 - d1, V3 = d1 - d3 and stores them as 128-B rows [hi 32 | lo 32]
+//    at row (hy * 4 + xi) * PW + p (PW = TW / 2 pairs per tile row: consecutive pairs are consecutive rows, as
+//    consecutive pixels are in the direct walk). 16-B slot XOR: (p >> 1) & 7 on 8 x 32 tiles; on 16 x 16 tiles
+//    ((p >> 1) & 3) | (hy & 1) << 2, so the four tile rows of a 16-lane ds_read_b128 group (two pair quads each,
+//    rows y, y + 1 and y + 2, y + 3 apart by one and three halo rows) land on 16 distinct (row parity, slot).
+//    Every thread loads the four columns of its pairs itself (columns shared by neighbouring pairs come from L1).
+//  * V is 72-80 KB, so there is ONE V buffer (as SH): the next chunk's halo, register-staged since step TA, is
+//    transformed and written after a barrier at the chunk's last step. (Two buffers of 16-channel half-chunks
+//    were not built: they halve the channels per barrier of a loop that already has 12 / 9 the barriers.)
+//  * B: the second weight image (weights.cpp prep_split_walk: U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 +
+//    g2) / 2, U3 = g2 along kx, K order ky, xi, ci) through the same ring, one 16-KB slot per step.
+//  * Each wave keeps four accumulator planes M_xi (wave tile 32 pairs x BN / 2: 4 x TN x 16 registers); the
+//    epilogue forms out[2p] = M0 + M1 + M2 and out[2p + 1] = M1 - M2 - M3 in registers while parking the tile.
+template <int TH, int TW, int BN, int WM, int WN, int D, int NSLOT, int SH, int PREC, int WALK = 0>
 __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 8 ? 4 : 2) : 1)) void conv_x6_kernel(ConvArgs a, int tiles_x, int tiles_y, int n_sp,
                                                                int ntn, int nchunks) {
   constexpr int NW = WM * WN, NT = 64 * NW;
   constexpr int BM = TH * TW;
-  constexpr int TM = BM / WM / 32;
+  constexpr int MR = WALK ? BM / 2 : BM;    // GEMM rows of the workgroup (walk: output pairs)
+  constexpr int NPL = WALK ? 4 : 1;         // accumulator planes
+  constexpr int NSTEP = WALK ? 12 : 9;      // steps per chunk
+  constexpr int PW = TW / 2;                // walk: pairs per tile row
+  constexpr int TM = MR / WM / 32;
   constexpr int TN = BN / WN / 32;
-  static_assert(TM >= 1 && TN >= 1 && TM * WM * 32 == BM && TN * WN * 32 == BN, "wave tiling");
+  static_assert(TM >= 1 && TN >= 1 && TM * WM * 32 == MR && TN * WN * 32 == BN, "wave tiling");
   static_assert(NSLOT >= D + 1 && D >= 1 && D <= 8, "ring");
+  static_assert(!WALK || (PREC == 0 && SH == 0 && NW == 8 && TM == 1 && (PW == 8 || PW == 16)), "walk forms");
+  constexpr bool ONEBUF = SH || WALK;       // one halo buffer
   constexpr int P = TW + 2;                 // halo row pitch (pixels); even
-  constexpr int HP = (TH + 2) * P;          // halo pixels
+  constexpr int HP = WALK ? (TH + 2) * PW * 4 : (TH + 2) * P;  // halo pixels (walk: V rows)
   constexpr int ABYTES = HP * 128;          // one split halo buffer
   constexpr int BIMG = BN * 64;             // one B image of one ring slot
   constexpr int BSLOT = 2 * BIMG;
@@ -167,9 +190,10 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   static_assert(BPS >= 1 && (2 * BQ) % NW == 0 && BQ % BPS == 0, "B DMA split over the waves");
   constexpr int CH = PREC ? 64 : 32;           // input channels per K chunk
   constexpr int QP = CH / 4;                   // float4 quads per halo pixel per chunk
-  constexpr int ALD = (HP * QP + NT - 1) / NT;  // halo float4 loads per thread per chunk
+  constexpr int AE = ((TH + 2) * PW * QP + NT - 1) / NT;  // walk: (halo row, pair, quad) elements per thread
+  constexpr int ALD = WALK ? 4 * AE : (HP * QP + NT - 1) / NT;  // halo float4 loads per thread per chunk
   constexpr int TA = 1;                        // tap step at which the next chunk's halo is issued
-  constexpr int NHB = SH ? 1 : 2;          // halo buffers
+  constexpr int NHB = ONEBUF ? 1 : 2;      // halo buffers
   constexpr int B_OFF = NHB * ABYTES;
   constexpr int LDS_MAIN = NHB * ABYTES + NSLOT * BSLOT, LDS_EPI = BM * BN * 4;
   __shared__ __attribute__((aligned(1024))) char lds[LDS_MAIN > LDS_EPI ? LDS_MAIN : LDS_EPI];
@@ -206,7 +230,7 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   // hofs: element offset of (pixel, 4q) at chunk 0, or -1 (zero fill); hwad: LDS byte offset (in a
   // halo buffer) of the hi 8 bytes (bf16: of the quad's 8 bytes), -1 = no write. Kept in registers for
   // 8-wave workgroups, recomputed per use by 4-wave ones (ALD = 11), whose register file is the limit.
-  constexpr bool HKEEP = NW == 8 && ALD <= 12 && !SH;
+  constexpr bool HKEEP = NW == 8 && ALD <= 12 && !SH && !WALK;
   auto hofs_of = [&](int i) {
     const int e = tid + NT * i;
     const int px = e / QP, q = e % QP;
@@ -230,10 +254,34 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
       hwad[i] = hwad_of(i);
     }
   }
+  // walk: element e = tid + NT i -> quad e & 7 of pair (e >> 3) % PW of halo row (e >> 3) / PW; its loads 4 i + k
+  // are the halo columns 2p + k, k = 0..3 (d_k above). Recomputed per chunk from an opaque copy of tid: hoisted out of
+  // the K loop, the offsets would not fit the register file beside the four accumulator planes.
+  auto opaque_tid = [&]() {
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    return t;
+  };
   x6f4 hr[ALD];
   auto halo_issue = [&](int c) {
     const bool cv = c < nchunks;
     const int co = c * CH;
+    if constexpr (WALK) {
+      const int tq = opaque_tid();
+#pragma unroll
+      for (int i = 0; i < AE; ++i) {
+        const int pr = (tq + NT * i) >> 3, q = tq & 7;
+        const int hy = pr / PW, p = pr - hy * PW;
+        const int iy = oy0 - 1 + hy, ix0 = ox0 - 1 + 2 * p;
+        const bool rv = cv && hy < TH + 2 && (unsigned)iy < (unsigned)a.H;
+        const int ho = (int)(nimg * a.in_sn + iy * a.in_sh + ix0 * a.in_sw) + 4 * q + co;
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          hr[4 * i + k] = vload6(rin, (rv && (unsigned)(ix0 + k) < (unsigned)a.W)
+                                          ? (uint32_t)(ho + k * (int)a.in_sw) * 4u : kOOB6);
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < ALD; ++i) {
       const int ho = HKEEP ? hofs[HKEEP ? i : 0] : hofs_of(i);
@@ -246,6 +294,27 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   };
   auto halo_store = [&](int buf) {
     char* base = lds + buf * ABYTES;
+    if constexpr (WALK) {
+      const int tq = opaque_tid();
+#pragma unroll
+      for (int i = 0; i < AE; ++i) {
+        const int pr = (tq + NT * i) >> 3, q = tq & 7;
+        const int hy = pr / PW, p = pr - hy * PW;
+        if (hy >= TH + 2) continue;
+        const int swz = PW == 8 ? ((p >> 1) & 3) | ((hy & 1) << 2) : (p >> 1) & 7;
+        const int hw = (hy * 4 * PW + p) * 128 + ((((q >> 1) ^ swz) & 7) << 4) + ((q & 1) << 3);
+        const x6f4 d0 = hr[4 * i], d1 = hr[4 * i + 1], d2 = hr[4 * i + 2], d3 = hr[4 * i + 3];
+        const x6f4 v[4] = {d0 - d2, d1 + d2, d2 - d1, d1 - d3};
+#pragma unroll
+        for (int xi = 0; xi < 4; ++xi) {
+          uint2 hi, lo;
+          split4(v[xi], hi, lo);
+          *reinterpret_cast<uint2*>(base + xi * PW * 128 + hw) = hi;
+          *reinterpret_cast<uint2*>(base + xi * PW * 128 + (hw ^ 64)) = lo;
+        }
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < ALD; ++i) {
       const int hw = HKEEP ? hwad[HKEEP ? i : 0] : hwad_of(i);
@@ -273,16 +342,20 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
     const int ls = (lane & 3) ^ ((c >> 2) & 3);
     const int n = n0 + c;
     bok[j] = n < a.Cout;
-    boff[j] = (uint32_t)(n * (int)a.ldh + ls * 8) * 2u;
+    boff[j] = (uint32_t)(n * (int)(WALK ? a.ldh2 : a.ldh) + ls * 8) * 2u;
     brow[j] = rb;
   }
   const bool bimg_lo = (wave * BPS) / BQ == 1;
   // f16x3: the second image of a slot is the lo split image; bf16: channels 32..63 of the same image
-  const x6i4 rwb = rsrc6((bimg_lo && !PREC) ? (const void*)a.wl : (const void*)a.wh);
+  const x6i4 rwb = WALK ? rsrc6(bimg_lo ? (const void*)a.wl2 : (const void*)a.wh2)
+                        : rsrc6((bimg_lo && !PREC) ? (const void*)a.wl : (const void*)a.wh);
   const uint32_t kb_lo = (PREC && bimg_lo) ? 64u : 0u;
   auto b_issue = [&](int slot, int tap, int c) {
     const bool cv = c < nchunks;
-    const uint32_t kb = (uint32_t)(tap * Cin + c * CH) * 2u + kb_lo;
+    // (walk: the uniform K offset pinned to a scalar register per step - otherwise the loop optimiser keeps one
+    // running per-lane offset per step and DMA, 24 registers the walk does not have)
+    const uint32_t kbv = (uint32_t)(tap * Cin + c * CH) * 2u + kb_lo;
+    const uint32_t kb = WALK ? (uint32_t)__builtin_amdgcn_readfirstlane((int)kbv) : kbv;
 #pragma unroll
     for (int j = 0; j < BPS; ++j) {
       const uint32_t dst = lds_u32 + B_OFF + slot * BSLOT + (bimg_lo ? BIMG : 0) + brow[j] * 64;
@@ -297,6 +370,12 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     const int m = (wm * TM + i) * 32 + li;
+    if constexpr (WALK) {  // pair m = (y, p): V row (ky 0, xi 0); [0] only
+      const int y = m / PW, p = m % PW;
+      const int swz = PW == 8 ? ((p >> 1) & 3) | ((y & 1) << 2) : (p >> 1) & 7;
+      aad[i][0] = aad[i][1] = aad[i][2] = (y * 4 * PW + p) * 128 + (((hh ^ swz) & 7) << 4);
+      continue;
+    }
     const int y = m / TW, x = m % TW;
 #pragma unroll
     for (int kw = 0; kw < 3; ++kw) aad[i][kw] = (y * P + x + kw) * 128 + (((hh ^ ((x + kw) >> 1)) & 7) << 4);
@@ -308,9 +387,9 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
     bad_[j] = c * 64 + (((hh ^ (c >> 2)) & 3) << 4);
   }
 
-  x6f16 acc[TM][TN];
+  x6f16 acc[NPL * TM][TN];  // walk: plane xi at [xi] (TM = 1)
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
+  for (int i = 0; i < NPL * TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -329,8 +408,11 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   Frag F0, F1;
   auto load_frag = [&](Frag& F, int slot, int c, auto TAP, auto S2) {
     constexpr int t = decltype(TAP)::value, s2 = decltype(S2)::value;
-    constexpr int kh = t / 3, kw = t % 3;
-    const char* abuf = lds + (SH ? 0 : (c & 1)) * ABYTES + kh * P * 128;
+    // walk: step t = (ky, xi); the halo row parity enters the 16 x 16 tile's slot XOR (bit 2 of the slot: byte 64)
+    constexpr int kh = WALK ? t / 4 : t / 3, kw = WALK ? 0 : t % 3;
+    constexpr int aofs = WALK ? (kh * 4 + t % 4) * PW * 128 : kh * P * 128;
+    constexpr int axor = (WALK && PW == 8 && (kh & 1)) ? 64 : 0;
+    const char* abuf = lds + (ONEBUF ? 0 : (c & 1)) * ABYTES + aofs;
     const char* bbuf = lds + B_OFF + slot * BSLOT;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -340,25 +422,26 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      const int o = aad[i][kw] ^ (32 * s2);
+      const int o = aad[i][kw] ^ (32 * s2) ^ axor;
       F.ah[i] = *reinterpret_cast<const x6h8*>(abuf + o);
       F.al[i] = *reinterpret_cast<const x6h8*>(abuf + (o ^ 64));
     }
   };
-  auto mfma_frag = [&](const Frag& F) {
+  auto mfma_frag = [&](const Frag& F, auto TAP) {
+    constexpr int pl = WALK ? decltype(TAP)::value % 4 : 0;  // the accumulator plane of the step
     if constexpr (PREC == 1) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6b8, F.ah[i]),
-                                                             __builtin_bit_cast(x6b8, F.bh[j]), acc[i][j], 0, 0, 0);
+          acc[pl * TM + i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6b8, F.ah[i]),
+                                                             __builtin_bit_cast(x6b8, F.bh[j]), acc[pl * TM + i][j], 0, 0, 0);
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6b8, F.al[i]),
-                                                             __builtin_bit_cast(x6b8, F.bl[j]), acc[i][j], 0, 0, 0);
+          acc[pl * TM + i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(x6b8, F.al[i]),
+                                                             __builtin_bit_cast(x6b8, F.bl[j]), acc[pl * TM + i][j], 0, 0, 0);
       return;
     }
     // small terms first, the hi x hi term last (independent accumulators interleaved)
@@ -366,17 +449,17 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.al[i], F.bh[j], acc[i][j], 0, 0, 0);
+        acc[pl * TM + i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.al[i], F.bh[j], acc[pl * TM + i][j], 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.ah[i], F.bl[j], acc[i][j], 0, 0, 0);
+        acc[pl * TM + i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.ah[i], F.bl[j], acc[pl * TM + i][j], 0, 0, 0);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.ah[i], F.bh[j], acc[i][j], 0, 0, 0);
+        acc[pl * TM + i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(F.ah[i], F.bh[j], acc[pl * TM + i][j], 0, 0, 0);
   };
 
   // Barrier opening step (c, t): this wave's B(c, t) DMAs have landed (vmcnt = memory ops issued
@@ -387,12 +470,12 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   auto open_step = [&](int c, auto TAP, auto FIRST) {
     constexpr int t = decltype(TAP)::value;
     constexpr bool first = decltype(FIRST)::value;
-    constexpr int N = (D - 1) * BPS + (halo_in_window(t, D, TA, first) ? ALD : 0);
+    constexpr int N = (D - 1) * BPS + (halo_in_window(t, D, TA, first, NSTEP) ? ALD : 0);
     step_barrier<N>();
-    constexpr int tn = (t + D) % 9;
+    constexpr int tn = (t + D) % NSTEP;
     int ns = slot + D;
     if (ns >= NSLOT) ns -= NSLOT;
-    b_issue(ns, tn, t + D >= 9 ? c + 1 : c);
+    b_issue(ns, tn, t + D >= NSTEP ? c + 1 : c);
     if constexpr (t == TA) halo_issue(c + 1);
   };
 
@@ -412,31 +495,32 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   auto step = [&](int c, auto TAP, auto FIRST) {
     constexpr int t = decltype(TAP)::value;
     constexpr bool first = decltype(FIRST)::value;
+    constexpr int TL = NSTEP - 1;  // the chunk's last step
     if constexpr (!PIPE) {
       load_frag(F0, slot, c, TAP, std::integral_constant<int, 0>());
-      mfma_frag(F0);
+      mfma_frag(F0, TAP);
       load_frag(F0, slot, c, TAP, std::integral_constant<int, 1>());
-      mfma_frag(F0);
-      if constexpr (t == 8) {
-        wait_vm<(8 - TA) * BPS>();
+      mfma_frag(F0, TAP);
+      if constexpr (t == TL) {
+        wait_vm<(TL - TA) * BPS>();
         halo_tie();
         // every wave's fragment reads of this chunk's halo have returned
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         halo_store(0);
       }
       if (++slot == NSLOT) slot = 0;
-      open_step(t == 8 ? c + 1 : c, std::integral_constant<int, (t + 1) % 9>(),
-                std::integral_constant<bool, first && t != 8>());
+      open_step(t == TL ? c + 1 : c, std::integral_constant<int, (t + 1) % NSTEP>(),
+                std::integral_constant<bool, first && t != TL>());
       return;
     }
     load_frag(F1, slot, c, TAP, std::integral_constant<int, 1>());
     __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead of the MFMAs they overlap
-    mfma_frag(F0);
-    if constexpr (t == 8) {
-      // the halo of chunk c+1 was issued when step TA opened; younger: B issued at steps TA+1 .. 8
-      wait_vm<(8 - TA) * BPS>();
+    mfma_frag(F0, TAP);
+    if constexpr (t == TL) {
+      // the halo of chunk c+1 was issued when step TA opened; younger: B issued at steps TA+1 .. TL
+      wait_vm<(TL - TA) * BPS>();
       halo_tie();
-      if constexpr (SH) {
+      if constexpr (ONEBUF) {
         // every wave's fragment reads of this chunk's halo (the F1 reads above) have returned
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         halo_store(0);
@@ -444,16 +528,19 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
         halo_store((c + 1) & 1);
       }
     }
-    constexpr int t1 = (t + 1) % 9;
-    const int c1 = t == 8 ? c + 1 : c;
+    constexpr int t1 = (t + 1) % NSTEP;
+    const int c1 = t == TL ? c + 1 : c;
     if (++slot == NSLOT) slot = 0;
-    open_step(c1, std::integral_constant<int, t1>(), std::integral_constant<bool, first && t != 8>());
+    open_step(c1, std::integral_constant<int, t1>(), std::integral_constant<bool, first && t != TL>());
     load_frag(F0, slot, c1, std::integral_constant<int, t1>(), std::integral_constant<int, 0>());
     __builtin_amdgcn_sched_barrier(0);
-    mfma_frag(F1);
+    mfma_frag(F1, TAP);
     __builtin_amdgcn_sched_barrier(0);
   };
   auto chunk = [&](int c, auto FIRST) {
+    // (walk: 12 steps return the 4-slot ring to where it began; hidden from the compiler, which would otherwise
+    // hoist every step's slot addresses out of the K loop, into registers the walk does not have)
+    if constexpr (WALK) asm volatile("" : "+s"(slot));
     step(c, std::integral_constant<int, 0>(), FIRST);
     step(c, std::integral_constant<int, 1>(), FIRST);
     step(c, std::integral_constant<int, 2>(), FIRST);
@@ -463,6 +550,11 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
     step(c, std::integral_constant<int, 6>(), FIRST);
     step(c, std::integral_constant<int, 7>(), FIRST);
     step(c, std::integral_constant<int, 8>(), FIRST);
+    if constexpr (WALK) {
+      step(c, std::integral_constant<int, 9>(), FIRST);
+      step(c, std::integral_constant<int, 10>(), FIRST);
+      step(c, std::integral_constant<int, 11>(), FIRST);
+    }
   };
   X6_STAMP(1);
   chunk(0, std::true_type());
@@ -489,7 +581,7 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   constexpr int IT = BM / (NT / QN);  // pixels per thread
   // (8-wave workgroups: up to 16 quads - the fragment / halo registers are dead by now; ~1 % on the BN = 128
   // layers, same-box A/B)
-  constexpr bool EARLY = IT <= (NW == 8 && !SH ? 16 : 8);
+  constexpr bool EARLY = IT <= (NW == 8 && !SH ? 16 : 8) && !WALK;
   x6f4 rv[IT];
   int ooff[IT];
   auto load_res = [&]() {
@@ -505,22 +597,37 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
   if constexpr (EARLY) load_res();
   x6f4 scl = {0.f, 0.f, 0.f, 0.f}, bia = {0.f, 0.f, 0.f, 0.f};
   if (nv) {
-    scl = *reinterpret_cast<const x6f4*>(a.wsinv + nq) * a.alpha;
+    scl = *reinterpret_cast<const x6f4*>((WALK ? a.wsinv2 : a.wsinv) + nq) * a.alpha;
     if (a.bias) bia = *reinterpret_cast<const x6f4*>(a.bias + nq);
   }
   float* ct = reinterpret_cast<float*>(lds);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
+  bool bad = false;
+  if constexpr (WALK) {
+    // pair m = (y, p) -> tile pixels 2m (x = 2p) and 2m + 1; a non-finite value in any plane reaches one of them
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-        ct[m * BN + (wn * TN + j) * 32 + li] = acc[i][j][r];
+        const int m = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+        const float m0 = acc[0][j][r], m1 = acc[1][j][r], m2 = acc[2][j][r], m3 = acc[3][j][r];
+        const float ev = m0 + m1 + m2, od = m1 - m2 - m3;
+        bad |= !(__builtin_isfinite(ev) && __builtin_isfinite(od));
+        ct[(2 * m) * BN + (wn * TN + j) * 32 + li] = ev;
+        ct[(2 * m + 1) * BN + (wn * TN + j) * 32 + li] = od;
       }
+  } else {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int m = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+          ct[m * BN + (wn * TN + j) * 32 + li] = acc[i][j][r];
+        }
+  }
   __syncthreads();
   if constexpr (!EARLY) load_res();
-  bool bad = false;
 #pragma unroll
   for (int k = 0; k < IT; ++k) {
     if (ooff[k] < 0) continue;
@@ -569,7 +676,7 @@ __global__ __launch_bounds__(64 * WM * WN, SH >= 2 ? SH + 1 : (SH ? (WM * WN == 
 #endif
 }
 
-template <int TH, int TW, int BN, int WM, int WN, int D, int NSLOT, int SH, int PREC>
+template <int TH, int TW, int BN, int WM, int WN, int D, int NSLOT, int SH, int PREC, int WALK = 0>
 static void launch_x6_one(const ConvArgs& a_in, hipStream_t st, ConvRoute& r) {
   ConvArgs a = a_in;
   // fused token pooling: whole tiles only, windows inside tiles, 16-B aligned channel quads
@@ -587,7 +694,8 @@ static void launch_x6_one(const ConvArgs& a_in, hipStream_t st, ConvRoute& r) {
                                   std::to_string(BN) + "," + std::to_string(WM) + "," + std::to_string(WN) +
                                   (PREC ? ",bf16>" : ">");
   r.config = name.c_str();
-  hipLaunchKernelGGL((conv_x6_kernel<TH, TW, BN, WM, WN, D, NSLOT, SH, PREC>), dim3(n_sp * ntn), dim3(64 * WM * WN), 0,
+  r.walk = WALK ? "f23" : "";
+  hipLaunchKernelGGL((conv_x6_kernel<TH, TW, BN, WM, WN, D, NSLOT, SH, PREC, WALK>), dim3(n_sp * ntn), dim3(64 * WM * WN), 0,
                      st, a, tiles_x, tiles_y, n_sp, ntn, a.Cin / (PREC ? 64 : 32));
   DD_HIP_CHECK(hipGetLastError());
 }
@@ -602,6 +710,19 @@ static void launch_x6_cfg(const ConvArgs& a, hipStream_t st, ConvRoute& r) {
     if (a.prec == 1) throw std::runtime_error("conv_x6: bf16 takes the 8-wave configurations");
   }
   launch_x6_one<TH, TW, BN, WM, WN, D, NSLOT, SH, 0>(a, st, r);
+}
+
+// The shapes routed to the F(2,3) walk by default: those whose walk launch measured at least 5 % faster than the
+// direct one at the benchmark batch, slowest walk run against fastest direct run (profiles/x6_walk_ab.md).
+// Walk against direct, median of five alternating runs at B = 64: image layer 2 -11.8 %, layer 3 -14.5 %, layer 4
+// -15.3 %, LiDAR layer 2 -9.2 %. Measured and not routed: LiDAR layer 3 (16 x 16 maps, the BN = 64 form, -3.1 %) and
+// the Cin = 64 layer-1 convs (+2 % against their 4-wave form).
+static bool x6_walk_routed(const ConvArgs& a) {
+  static const int kShapes[][4] = {  // H, W, Cin, Cout
+      {32, 128, 128, 128}, {16, 64, 256, 256}, {8, 32, 512, 512}, {32, 32, 128, 128}};
+  for (const auto& s : kShapes)
+    if (a.H == s[0] && a.W == s[1] && a.Cin == s[2] && a.Cout == s[3]) return true;
+  return false;
 }
 
 // Returns false when the conv is not a 3x3 / stride 1 / pad 1 f16x3 / bf16 conv this kernel covers (the
@@ -642,6 +763,23 @@ bool launch_conv_x6(const ConvArgs& a, hipStream_t st, ConvRoute& r) {
   const bool sh4 = a.prec == 0 && a.Cin <= 64;
   const bool b128 = bn128;
 #define X6(TH, TW, BN, WM, WN, D, NS, SH) launch_x6_cfg<TH, TW, BN, WM, WN, D, NS, SH>(a, st, r)
+#define X6W(TH, TW, BN, WM, WN, D, NS) launch_x6_one<TH, TW, BN, WM, WN, D, NS, 0, 0, 1>(a, st, r)
+  // The F(2,3) walk (kernel header): f16x3 with the second weight image, on the 8-wave forms <16,16,128,4,2>,
+  // <8,32,128,4,2> and <16,16,64,4,2>. DDMI_X6_WALK: 0 never; unset / 1: the launches whose form is one of those
+  // three and whose shape x6_walk_routed() lists; 2: wherever the kernel covers the shape - the launch's own form
+  // when it is one of the three, otherwise (small grids, the 4-wave and BN = 64 8 x 32 forms) BN = 128 when
+  // Cout > 64 and <16,16,64,4,2> below - for tests and A/B runs.
+  const char* we = getenv("DDMI_X6_WALK");
+  const int wk = we ? atoi(we) : 1;
+  const bool wimg = a.prec == 0 && a.wh2 && a.wl2 && a.wsinv2 && al16(a.wsinv2) && a.ldh2 == 12 * (int64_t)a.Cin &&
+                    (int64_t)a.Cout * a.ldh2 < (int64_t(1) << 30);
+  const bool wany = wk == 2 && wimg;
+  auto walk_by_cout = [&]() {  // DDMI_X6_WALK=2 where the launch's own form has no walk
+    if (wide) X6W(8, 32, 128, 4, 2, 3, 4);
+    else if (a.Cout > 64) X6W(16, 16, 128, 4, 2, 3, 4);
+    else X6W(16, 16, 64, 4, 2, 2, 3);
+  };
+  const bool wr = wany || (wk == 1 && wimg && x6_walk_routed(a));
   // small grids (batches of a few scenes): the routed form would run fewer than 128 workgroups, each through the
   // whole K loop; 8 x 8 pixel tiles x 64 channels (4 waves of 32 x 32) give 4-8x the workgroups at a quarter of the
   // work per K step. The K order (32-channel chunk, tap, k16 half) is every form's: bit-identical results.
@@ -651,23 +789,29 @@ bool launch_conv_x6(const ConvArgs& a, hipStream_t st, ConvRoute& r) {
     const char* se = getenv("DDMI_X6_SMALL");
     const int sm = se ? atoi(se) : 1;
     if (sm == 2 || (wgs < 128 && sm != 0)) {
-      X6(8, 8, 64, 2, 2, 2, 3, 0);
+      if (wany && (!wide || a.Cout > 64)) walk_by_cout(); else X6(8, 8, 64, 2, 2, 2, 3, 0);
       return true;
     }
   }
   if (wide) {
     if (b128) {
-      X6(8, 32, 128, 4, 2, 3, 4, 0);
+      if (wr) X6W(8, 32, 128, 4, 2, 3, 4); else X6(8, 32, 128, 4, 2, 3, 4, 0);
     } else {
-      if (sh4) X6(8, 32, 64, 4, 1, 2, 3, 1); else X6(8, 32, 64, 4, 2, 2, 3, 0);
+      if (wany && a.Cout > 64) walk_by_cout();
+      else if (sh4) X6(8, 32, 64, 4, 1, 2, 3, 1);
+      else X6(8, 32, 64, 4, 2, 2, 3, 0);
     }
   } else {
     if (b128) {
-      X6(16, 16, 128, 4, 2, 3, 4, 0);
+      if (wr) X6W(16, 16, 128, 4, 2, 3, 4); else X6(16, 16, 128, 4, 2, 3, 4, 0);
     } else {
-      if (sh4) X6(16, 16, 64, 4, 1, 2, 3, 1); else X6(16, 16, 64, 4, 2, 2, 3, 0);
+      if (sh4 && wany) walk_by_cout();
+      else if (sh4) X6(16, 16, 64, 4, 1, 2, 3, 1);
+      else if (wany) X6W(16, 16, 64, 4, 2, 2, 3);  // never routed: -3 % on LiDAR layer 3, the one shape that takes it
+      else X6(16, 16, 64, 4, 2, 2, 3, 0);
     }
   }
+#undef X6W
 #undef X6
   return true;
 }

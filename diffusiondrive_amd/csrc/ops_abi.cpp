@@ -15,7 +15,9 @@ thread_local std::string g_op_err;
 // dd_op_last_kernel: the configuration of the calling thread's last conv / GEMM launch (a dispatch that launched
 // nothing leaves it)
 thread_local const char* g_op_kernel = "";
+thread_local const char* g_op_walk = "";
 void ran(const ddmi::ConvRoute& r) {
+  if (*r.config) g_op_walk = r.walk;
   if (*r.config) g_op_kernel = r.config;
 }
 
@@ -42,6 +44,8 @@ extern "C" {
 const char* dd_op_last_error(void) { return g_op_err.c_str(); }
 
 const char* dd_op_last_kernel(void) { return g_op_kernel; }
+
+const char* dd_op_last_walk(void) { return g_op_walk; }
 
 int dd_op_split_weights(const float* w, int rows, int K, uint16_t* hi, uint16_t* lo, uint16_t* b16, float* sinv,
                         int* ldh_out) {
@@ -146,6 +150,18 @@ static void attach_split(ConvArgs& a, const Arena& ar, const SplitW& x, int prec
   a.flags = flags;
 }
 
+// The ops build the F(2,3) walk image (conv_x6) of every 3 x 3 / stride 1 / pad 1 conv with Cin % 32 == 0, whatever
+// its size: DDMI_X6_WALK=2 then reaches the walk at test shapes.
+static bool walk_geom(int KH, int KW, int stride, int pad, int Cin) {
+  return KH == 3 && KW == 3 && stride == 1 && pad == 1 && Cin % 32 == 0;
+}
+static void attach_walk(ConvArgs& a, const Arena& ar, const SplitW& xw) {
+  a.wh2 = reinterpret_cast<const uint16_t*>(ar.ptr(xw.hi));
+  a.wl2 = reinterpret_cast<const uint16_t*>(ar.ptr(xw.lo));
+  a.wsinv2 = ar.ptr(xw.sinv);
+  a.ldh2 = xw.ldh;
+}
+
 int dd_op_conv2d(const float* in, int B, int H, int W, int Cin, const float* wgt, const float* bias, const float* res,
                  float* out, int Cout, int KH, int KW, int stride, int pad, int relu, void* stream) {
   return op_guard([&] {
@@ -165,10 +181,14 @@ int dd_op_conv2d_x3(const float* in, int B, int H, int W, int Cin, const float* 
     DD_HIP_CHECK(hipMemcpy(hw.data(), wgt, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
     Arena ar;
     const SplitW x = prep_split(ar, hw.data(), Cout, K);
+    const bool walk = prec == 0 && walk_geom(KH, KW, stride, pad, Cin);
+    SplitW xw;
+    if (walk) xw = prep_split_walk(ar, hw.data(), Cout, Cin);
     ar.upload();
     ConvArgs a = conv2d_args(in, B, H, W, Cin, wgt, bias, res, out, Cout, KH, KW, stride, pad, relu);
     if (prec != 0 && prec != 1) throw std::invalid_argument("prec must be 0 (f16x3) or 1 (bf16)");
     attach_split(a, ar, x, prec, flags);
+    if (walk) attach_walk(a, ar, xw);
     // K-split scratch, as the forward provides it (runtime.cpp: run): small grids may take conv_x3's split form
     const int64_t mo = (int64_t)B * a.Ho * a.Wo * Cout;
     float* part = nullptr;
@@ -442,8 +462,12 @@ int dd_op_conv_view(dd_op_conv_desc* d, void* stream) {
       std::vector<float> hw((size_t)d->Cout * d->ldb);
       DD_HIP_CHECK(hipMemcpy(hw.data(), d->wgt, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
       const SplitW x = prep_split(ar, hw.data(), d->Cout, (int)d->ldb);
+      const bool walk = d->mode == 1 && !sliced && walk_geom(d->KH, d->KW, d->stride, d->pad, d->Cin);
+      SplitW xw;
+      if (walk) xw = prep_split_walk(ar, hw.data(), d->Cout, d->Cin);
       ar.upload();
       attach_split(a, ar, x, d->mode - 1, d->flags);
+      if (walk) attach_walk(a, ar, xw);
     }
     if (sliced) slice_k(a, d->k0, d->ldb);
     if (d->ln_out) fold_ln(a, d->ln_out, d->ln_g, d->ln_b);

@@ -1210,6 +1210,7 @@ class Model {
                " K=" + std::to_string(c.KH * c.KW * c.Cin) + " k=" + std::to_string(c.KH) + " s=" +
                std::to_string(c.stride) + " z=" + std::to_string(c.batch) + " HW=" + std::to_string(c.H) + "x" +
                std::to_string(c.W) + " cfg=" + route.config;  // the dispatcher's choice
+      if (route.walk[0]) detail += std::string(" walk=") + route.walk;
     }
     if (note) detail += (detail.empty() ? "" : " ") + std::string(note);
     pending.push_back({name, flops, bytes >= 0.0 ? bytes : (shape ? conv_algo_bytes(*shape) : 0.0), a, b, detail});
@@ -1237,7 +1238,7 @@ class Model {
   }
 
   // the weight of a launch: the fp32 image and bias, and the split images when the mode routes to them
-  ConvArgs attach(ConvArgs a, size_t w, size_t b, const SplitW& x) {
+  ConvArgs attach(ConvArgs a, size_t w, size_t b, const SplitW& x, const SplitW* xw = nullptr) {
     a.wgt = W(w);
     a.bias = W(b);
     if (gemm_mode == DD_GEMM_FP32 || x.hi == kNone) return a;
@@ -1247,6 +1248,12 @@ class Model {
     a.wsinv = W(x.sinv);
     a.ldh = x.ldh;
     a.flags = num_flags;
+    if (xw && xw->hi != kNone && a.prec == 0) {  // the F(2,3) walk image (conv_x6)
+      a.wh2 = reinterpret_cast<const uint16_t*>(W(xw->hi));
+      a.wl2 = reinterpret_cast<const uint16_t*>(W(xw->lo));
+      a.wsinv2 = W(xw->sinv);
+      a.ldh2 = xw->ldh;
+    }
     return a;
   }
   // The tail of every conv / GEMM launch (a: built by common.h's builders, weight attached).
@@ -1272,7 +1279,7 @@ class Model {
   // conv on strided NHWC views; pool: also fused into it when its square windows tile the output exactly
   ConvRoute conv(const Conv& c, View4 in, int N, int H, int Wd, View4 out, bool relu, View4 res = {},
                  const PoolSpec* pool = nullptr) {
-    ConvArgs a = attach(conv_args(in, N, H, Wd, c.cin, geom(c), out, relu, res), c.w, c.b, c.x3);
+    ConvArgs a = attach(conv_args(in, N, H, Wd, c.cin, geom(c), out, relu, res), c.w, c.b, c.x3, &c.x3w);
     if (pool && a.Ho % pool->oh == 0 && a.Wo % pool->ow == 0 && a.Ho / pool->oh == a.Wo / pool->ow)
       pool_into(a, a.Ho / pool->oh, pool->out, pool->add);
     return run(a, 2.0 * N * a.Ho * a.Wo * (double)c.cout * c.k * c.k * c.cin_real, true);

@@ -109,17 +109,17 @@ size_t Arena::add_zero(size_t n) {
 // [2^14, 2^15] (exact power-of-two scaling, no fp16 overflow, lo parts clear of the subnormal
 // range); hi = f16(w * s_r), lo = f16(w * s_r - hi), both RNE; sinv[r] = 1 / s_r. e <= kSplitMaxExp
 // (weights.h) keeps s_r and 1 / s_r normal fp32 numbers on rows below 2^-112; a zero row keeps s_r = 1.
-SplitW prep_split(Arena& ar, const float* w, int rows, int K) {
+SplitW prep_split(Arena& ar, const float* w, int rows, int K, bool bf16) {
   SplitW x;
   x.ldh = (K + 7) / 8 * 8;
   const size_t nh = (size_t)rows * x.ldh;  // halfs per image
   x.hi = ar.add_zero((nh + 1) / 2);
   x.lo = ar.add_zero((nh + 1) / 2);
-  x.b16 = ar.add_zero((nh + 1) / 2);
+  if (bf16) x.b16 = ar.add_zero((nh + 1) / 2);
   std::vector<float> sinv(rows, 1.f);
   _Float16* hi = reinterpret_cast<_Float16*>(ar.host(x.hi));
   _Float16* lo = reinterpret_cast<_Float16*>(ar.host(x.lo));
-  __bf16* b16 = reinterpret_cast<__bf16*>(ar.host(x.b16));
+  __bf16* b16 = bf16 ? reinterpret_cast<__bf16*>(ar.host(x.b16)) : nullptr;
   for (int r = 0; r < rows; ++r) {
     float amax = 0.f;
     for (int k = 0; k < K; ++k) amax = std::max(amax, std::fabs(w[(size_t)r * K + k]));
@@ -137,11 +137,33 @@ SplitW prep_split(Arena& ar, const float* w, int rows, int K) {
       const _Float16 h = (_Float16)v;
       hi[(size_t)r * x.ldh + k] = h;
       lo[(size_t)r * x.ldh + k] = (_Float16)(v - (float)h);
-      b16[(size_t)r * x.ldh + k] = (__bf16)v;
+      if (b16) b16[(size_t)r * x.ldh + k] = (__bf16)v;
     }
   }
   x.sinv = ar.add(sinv);
   return x;
+}
+
+SplitW prep_split_walk(Arena& ar, const float* w, int cout, int cin) {
+  std::vector<float> u((size_t)cout * 12 * cin);
+  for (int o = 0; o < cout; ++o)
+    for (int y = 0; y < 3; ++y)
+      for (int i = 0; i < cin; ++i) {
+        const float* g = w + (((size_t)o * 3 + y) * 3) * cin + i;
+        const double g0 = g[0], g1 = g[cin], g2 = g[2 * (size_t)cin];
+        float* d = u.data() + (((size_t)o * 3 + y) * 4) * cin + i;
+        d[0] = (float)g0;
+        d[cin] = (float)((g0 + g1 + g2) / 2);
+        d[2 * (size_t)cin] = (float)((g0 - g1 + g2) / 2);
+        d[3 * (size_t)cin] = (float)g2;
+      }
+  return prep_split(ar, u.data(), cout, 12 * cin, false);
+}
+
+// the channel pairs of the shapes conv_x6 routes to the walk (conv_x6.hip x6_walk_routed): the BasicBlock convs of
+// layers 2 to 4
+bool x6_walk_weight(int cout, int cin, int k, int stride, int pad) {
+  return k == 3 && stride == 1 && pad == 1 && cin == cout && (cin == 128 || cin == 256 || cin == 512);
 }
 
 void Arena::upload() {
@@ -187,6 +209,7 @@ Conv prep_conv(const BlobIndex& bx, Arena& ar, const std::string& wname, int cou
   for (int o = 0; o < cout; ++o) bl[o] = (float)shift[o];
   Conv c;
   c.x3 = prep_split(ar, wl.data(), cout, k * k * cin_p);
+  if (x6_walk_weight(cout, cin_p, k, stride, pad)) c.x3w = prep_split_walk(ar, wl.data(), cout, cin_p);
   c.w = ar.add(wl);
   c.b = any_bias ? ar.add(bl) : kNone;
   c.cout = cout;

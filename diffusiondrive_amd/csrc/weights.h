@@ -57,6 +57,7 @@ struct Conv {
   size_t w = kNone, b = kNone;
   int cout = 0, cin = 0, cin_real = 0, k = 1, stride = 1, pad = 0;
   SplitW x3;
+  SplitW x3w;  // the F(2,3) walk image (prep_split_walk), only for the convs conv_x6 can route to the walk
 };
 // nn.Linear weights [nout][nin].
 struct Lin {
@@ -75,7 +76,15 @@ Lin prep_linear(const BlobIndex& bx, Arena& ar, const std::string& prefix, int n
 Lin prep_linear_rows(const BlobIndex& bx, Arena& ar, const std::string& wname, const std::string& bname,
                      int rows_total, int nin, int row0, int nrows);
 // Split rows x K fp32 weights (host) into the f16x3 hi / lo images with per-row scale.
-SplitW prep_split(Arena& ar, const float* w, int rows, int K);
+// bf16: also the bf16 image (SplitW::b16)
+SplitW prep_split(Arena& ar, const float* w, int rows, int K, bool bf16 = true);
+// The F(2,3) walk image of a 3x3 conv weight w [cout][3][3][cin] (fp32, BN folded): per (co, ky, ci) the taps
+// g0, g1, g2 along kx become U0 = g0, U1 = (g0 + g1 + g2) / 2, U2 = (g0 - g1 + g2) / 2, U3 = g2 (computed in
+// double, rounded to fp32), laid out [cout][ky][xi][cin] and split like any other image (one scale per row over
+// its 12 cin entries; no bf16 image).
+SplitW prep_split_walk(Arena& ar, const float* w, int cout, int cin);
+// Which convs get the walk image: the 3x3 / stride 1 / pad 1 ones whose shape conv_x6 may route to the walk
+bool x6_walk_weight(int cout, int cin, int k, int stride, int pad);
 
 LNp prep_ln(const BlobIndex& bx, Arena& ar, const std::string& prefix, int c);
 

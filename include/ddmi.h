@@ -504,6 +504,8 @@ const char* dd_op_last_error(void);
 /* Kernel and tile configuration of the calling thread's last conv / GEMM launch (dd_op_* or forward), e.g.
  * "conv_x6<8,32,128,4,2>": lets tests prove which route a shape took. */
 const char* dd_op_last_kernel(void);
+/* The K walk of that launch: "f23" (conv_x6's Winograd F(2,3) walk along W) or "" (the direct walk). */
+const char* dd_op_last_walk(void);
 /* The host's f16x3 / bf16 weight split (weights.cpp:prep_split) on host pointers, no device call: w fp32
  * [rows][K] -> hi, lo (fp16 bits) and b16 (bf16 bits), each [rows][ldh] with ldh = K rounded up to 8 (padding
  * zero), sinv[rows] = 1 / s_r, *ldh_out = ldh. Any output may be null. */

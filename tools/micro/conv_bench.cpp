@@ -2,7 +2,9 @@
 // ddmi::launch_conv_gemm in f16x3 mode (the kernel the runtime would pick; DDMI_X6 / DDMI_X5 env
 // switches select variants) against the fp32-MFMA kernel on the same inputs.
 // Prints one line per shape: device ms per launch (HIP events, median of reps), algorithmic TF/s,
-// and max |f16x3 - fp32| / max |fp32|.
+// and max |f16x3 - fp32| / max |fp32|. Every 3x3 / stride 1 conv with Cin % 32 == 0 also gets the F(2,3) walk image, so
+// DDMI_X6_WALK=0 / 2 times conv_x6's direct walk against the Winograd one on the same shape (the last column names
+// the walk taken: tools/x6_walk_ab.sh alternates the two).
 //   build: tools/micro/build_conv_bench.sh     run: tools/micro/conv_bench [reps] [shape-substring]
 #include <hip/hip_runtime.h>
 
@@ -118,6 +120,9 @@ int main(int argc, char** argv) {
     }
     Arena ar;
     const SplitW x = prep_split(ar, hw.data(), sh.Cout, K);
+    const bool walk = sh.k == 3 && sh.s == 1 && sh.Cin % 32 == 0;
+    SplitW xw;
+    if (walk) xw = prep_split_walk(ar, hw.data(), sh.Cout, sh.Cin);
     ar.upload();
     ConvArgs a = conv_args(nhwc(din, sh.H, sh.W, sh.Cin), sh.B, sh.H, sh.W, sh.Cin,
                            ConvGeom{sh.k, sh.k, sh.s, pad, sh.Cout}, nhwc(dref, Ho, Wo, sh.Cout), 1,
@@ -151,6 +156,12 @@ int main(int argc, char** argv) {
     b.wsinv = ar.ptr(x.sinv);
     b.ldh = x.ldh;
     b.flags = flags;
+    if (walk) {
+      b.wh2 = reinterpret_cast<const uint16_t*>(ar.ptr(xw.hi));
+      b.wl2 = reinterpret_cast<const uint16_t*>(ar.ptr(xw.lo));
+      b.wsinv2 = ar.ptr(xw.sinv);
+      b.ldh2 = xw.ldh;
+    }
     CK(hipMemset(dout, 0xff, nout * 4));  // NaN fill: a skipped output shows up
     const float ms = timed(b);
     CK(hipStreamSynchronize(st));
@@ -192,7 +203,8 @@ int main(int argc, char** argv) {
       md = std::isfinite(d) ? std::max(md, d) : INFINITY;
     }
     const double fl = 2.0 * sh.B * Ho * Wo * (double)sh.Cout * K * (sh.Cin == 4 ? 3.0 / 4.0 : 1.0);
-    printf("%-12s %9.4f %9.1f %8.4f %10.3e\n", sh.name, ms, fl / ms * 1e-9, ms32, md / mx);
+    printf("%-12s %9.4f %9.1f %8.4f %10.3e %s %s\n", sh.name, ms, fl / ms * 1e-9, ms32, md / mx, route.config,
+           route.walk[0] ? route.walk : "direct");
     fflush(stdout);
     (void)hipFree(din);
     (void)hipFree(dw);
