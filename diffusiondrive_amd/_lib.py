@@ -102,6 +102,30 @@ class DDDrivableMaps(ctypes.Structure):
     ]
 
 
+class DDScoreParams(ctypes.Structure):
+    """dd_score_params: the weights, thresholds and angle bounds of dd_collisions / dd_pdm_aggregate
+    (include/ddmi.h)."""
+    _fields_ = [
+        ("progress_weight", ctypes.c_double), ("ttc_weight", ctypes.c_double), ("comfortable_weight", ctypes.c_double),
+        ("driving_direction_weight", ctypes.c_double), ("progress_distance_threshold", ctypes.c_double),
+        ("ttc_stopped_speed_threshold", ctypes.c_double), ("collision_stopped_speed_threshold", ctypes.c_double),
+        ("ahead_angle", ctypes.c_double), ("behind_angle", ctypes.c_double),
+    ]
+
+
+class DDObservations(ctypes.Structure):
+    """dd_observations: the tracked objects of G scenes as flat device arrays (include/ddmi.h)."""
+    _fields_ = [
+        ("boxes", c_void_p), ("valid", c_void_p), ("heading", c_void_p), ("flags", c_void_p),
+        ("scene_track_off", c_void_p), ("num_tracks", ctypes.c_int), ("num_times", ctypes.c_int),
+    ]
+
+
+class DDCenterlines(ctypes.Structure):
+    """dd_centerlines: the centerlines of G scenes as flat device arrays (include/ddmi.h)."""
+    _fields_ = [("verts", c_void_p), ("scene_off", c_void_p), ("num_verts", ctypes.c_int)]
+
+
 class DDOpView(ctypes.Structure):
     """dd_op_view: a strided (n, h, w, c) operand of the view-taking single-op entries (include/ddmi.h)."""
     _fields_ = [("p", c_void_p), ("sn", ctypes.c_int64), ("sh", ctypes.c_int64), ("sw", ctypes.c_int64),
@@ -176,6 +200,17 @@ _SIGS = {
     "dd_ego_areas": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDDrivableMaps), ctypes.c_int,
                                     ctypes.POINTER(DDAreaParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+    "dd_default_score_params": (None, [ctypes.POINTER(DDScoreParams)]),
+    "dd_collisions_work": (ctypes.c_size_t, [ctypes.c_int]),
+    "dd_collisions": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDObservations),
+                                     ctypes.POINTER(DDDrivableMaps), ctypes.c_int, ctypes.POINTER(DDAreaParams),
+                                     ctypes.POINTER(DDScoreParams), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p]),
+    "dd_progress": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDCenterlines), ctypes.c_int,
+                                   ctypes.POINTER(DDAreaParams), c_void_p, c_void_p]),
+    "dd_pdm_aggregate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.POINTER(DDScoreParams), c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
     "dd_set_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_set_schedule": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_get_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int)]),

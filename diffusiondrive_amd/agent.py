@@ -210,6 +210,22 @@ class DiffusionDriveAgent(_Base):
             states = states.to(torch.device("cuda", self._transfuser_model.device))
         return ego_areas(states, maps, params, coords)
 
+    def pdm_score(self, states, maps, observations, centerlines, ego_states=None, key: str = "trajectory", **kwargs):
+        """The whole PDM score on the GPU (``diffusiondrive_amd.simulate.pdm_score``): comfort, map compliance,
+        no-at-fault collision, time-to-collision, progress and the aggregation (pdm_scorer.py:114-183) of every
+        candidate of the (B, ..., 41, 11) float64 states ``simulate_trajectories`` returns, against the B scenes' maps,
+        tracked objects and centerlines (packed, or as ``pack_drivable_maps``, ``pack_observations`` and
+        ``pack_centerlines`` take them). With ``ego_states`` (B, 11), ``states`` is instead a forward's output dict (of
+        which ``key`` is read) or a (B, ..., 8, 3) tensor of poses, simulated first. Returns a ``PDMScores``. A host
+        tensor is moved to the model's device."""
+        from .simulate import pdm_score
+        if ego_states is not None:
+            states = self.simulate_trajectories(states, ego_states, key)
+        states = torch.as_tensor(states)
+        if states.device.type != "cuda":
+            states = states.to(torch.device("cuda", self._transfuser_model.device))
+        return pdm_score(states, maps, observations, centerlines, **kwargs)
+
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).
 TransfuserAgent = DiffusionDriveAgent

@@ -21,6 +21,9 @@ struct dd_sim_params;  // include/ddmi.h
 struct dd_comfort_params;
 struct dd_area_params;
 struct dd_drivable_maps;
+struct dd_score_params;
+struct dd_observations;
+struct dd_centerlines;
 
 namespace ddmi {
 
@@ -643,5 +646,21 @@ size_t ego_areas_work_doubles(int P);
 void launch_ego_areas(const double* states, int N, int per_group, const dd_drivable_maps& maps, int G,
                       const dd_area_params& p, int horizon, double* work, uint8_t* out_areas, double* out_scores,
                       double* out_progress, double* out_coords, hipStream_t st);
+
+// ---- collisions.hip: no-at-fault collision and TTC (dd_collisions); work = collisions_work_doubles(K) doubles (the
+// tracks' bounding boxes, filled by the first of the two launches). The parameters are checked by the caller.
+size_t collisions_work_doubles(int K);
+void launch_collisions(const double* states, const uint8_t* areas, int N, int per_group, const dd_observations& obs,
+                       const dd_drivable_maps& ix, int G, const dd_area_params& ap, const dd_score_params& sp,
+                       double* work, double* out_no_collision, double* out_collision_idx, double* out_ttc,
+                       double* out_ttc_idx, hipStream_t st);
+
+// ---- pdm_aggregate.hip: progress along the centerline (dd_progress) and the aggregation (dd_pdm_aggregate)
+void launch_progress(const double* states, int N, int per_group, const dd_centerlines& lines,
+                     double rear_axle_to_center, double* out_raw, hipStream_t st);
+void launch_pdm_aggregate(const double* no_collision, const double* drivable_area, const double* driving_direction,
+                          const double* raw_progress, const double* ttc, const uint8_t* comfort, int N, int per_group,
+                          const dd_score_params& sp, const double* progress_reference, double* out_score,
+                          double* out_progress, hipStream_t st);
 
 }  // namespace ddmi

@@ -17,6 +17,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -2755,6 +2756,147 @@ int dd_ego_areas(const double* states, int N, int per_group, const dd_drivable_m
           ": int(horizon / dt) must be in [0, 40]");
     ddmi::launch_ego_areas(states, N, per_group, *maps, G, *p, (int)steps, work, out_areas, out_scores, out_progress,
                            out_coords, static_cast<hipStream_t>(stream));
+  });
+}
+
+// ---- collisions, TTC, progress and the aggregation (collisions.hip, pdm_aggregate.hip): stateless, every argument
+// checked before any device work
+void dd_default_score_params(dd_score_params* p) {
+  if (!p) return;
+  p->progress_weight = 5.0;
+  p->ttc_weight = 5.0;
+  p->comfortable_weight = 2.0;
+  p->driving_direction_weight = 0.0;
+  p->progress_distance_threshold = 5.0;
+  p->ttc_stopped_speed_threshold = 5e-3;
+  p->collision_stopped_speed_threshold = 5e-2;
+  p->ahead_angle = 30.0 * (M_PI / 180.0);   // np.deg2rad(30): x * (pi / 180)
+  p->behind_angle = 150.0 * (M_PI / 180.0);
+}
+
+// the checks the three entries share: `bad` throws with the entry's name in front
+using BadFn = std::function<void(const std::string&)>;
+static void check_counts(const BadFn& bad, int N, int per_group, int G, bool with_G) {
+  if (N <= 0) bad("N = " + std::to_string(N) + " must be positive");
+  if (per_group <= 0) bad("per_group = " + std::to_string(per_group) + " must be positive");
+  if (N % per_group) bad("N = " + std::to_string(N) + " is not a multiple of per_group = " + std::to_string(per_group));
+  if (with_G && G != N / per_group)
+    bad("G = " + std::to_string(G) + " is not N / per_group = " + std::to_string(N / per_group));
+}
+
+static void check_score_params(const BadFn& bad, const dd_score_params& p) {
+  const struct { const char* field; double v; } fields[] = {
+      {"progress_weight", p.progress_weight},
+      {"ttc_weight", p.ttc_weight},
+      {"comfortable_weight", p.comfortable_weight},
+      {"driving_direction_weight", p.driving_direction_weight},
+      {"progress_distance_threshold", p.progress_distance_threshold},
+      {"ttc_stopped_speed_threshold", p.ttc_stopped_speed_threshold},
+      {"collision_stopped_speed_threshold", p.collision_stopped_speed_threshold},
+      {"ahead_angle", p.ahead_angle},
+      {"behind_angle", p.behind_angle}};
+  for (const auto& f : fields)
+    if (!std::isfinite(f.v) || f.v < 0.0)
+      bad(std::string("dd_score_params.") + f.field + " = " + std::to_string(f.v) + " must be finite and not negative");
+  if (!(((p.progress_weight + p.ttc_weight) + p.comfortable_weight) + p.driving_direction_weight > 0.0))
+    bad("dd_score_params.progress_weight + ttc_weight + comfortable_weight + driving_direction_weight is zero");
+  if (p.ahead_angle > p.behind_angle)
+    bad("dd_score_params.ahead_angle = " + std::to_string(p.ahead_angle) + " is above behind_angle = " +
+        std::to_string(p.behind_angle));
+}
+
+size_t dd_collisions_work(int K) { return ddmi::collisions_work_doubles(K); }
+
+int dd_collisions(const double* states, const uint8_t* areas, int N, int per_group, const dd_observations* obs,
+                  const dd_drivable_maps* ix, int G, const dd_area_params* ap, const dd_score_params* sp, double* work,
+                  double* out_no_collision, double* out_collision_time_idx, double* out_ttc, double* out_ttc_time_idx,
+                  void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_collisions: " + what); };
+    check_counts(bad, N, per_group, G, true);
+    if (!states) bad("states is null");
+    if (!areas) bad("areas is null");
+    if (!obs) bad("obs is null");
+    if (!ix) bad("intersections is null");
+    if (!ap) bad("area_params is null");
+    if (!sp) bad("score_params is null");
+    if (!work) bad("work is null");
+    if (!out_no_collision) bad("out_no_collision is null");
+    if (!out_collision_time_idx) bad("out_collision_time_idx is null");
+    if (!out_ttc) bad("out_ttc is null");
+    if (!out_ttc_time_idx) bad("out_ttc_time_idx is null");
+    if (!obs->scene_track_off) bad("dd_observations.scene_track_off is null");
+    if (obs->num_tracks < 0) bad("dd_observations.num_tracks = " + std::to_string(obs->num_tracks) + " is negative");
+    if (obs->num_times < 50)
+      bad("dd_observations.num_times = " + std::to_string(obs->num_times) + " is below 50 (TTC reads map t + 9)");
+    if (obs->num_tracks > 0) {
+      if (!obs->boxes) bad("dd_observations.boxes is null");
+      if (!obs->valid) bad("dd_observations.valid is null");
+      if (!obs->heading) bad("dd_observations.heading is null");
+      if (!obs->flags) bad("dd_observations.flags is null");
+    }
+    if (!ix->scene_poly_off) bad("dd_drivable_maps.scene_poly_off is null");
+    if (ix->num_polys < 0) bad("dd_drivable_maps.num_polys = " + std::to_string(ix->num_polys) + " is negative");
+    if (ix->num_polys > 0) {
+      if (!ix->verts) bad("dd_drivable_maps.verts is null");
+      if (!ix->ring_off) bad("dd_drivable_maps.ring_off is null");
+      if (!ix->poly_ring_off) bad("dd_drivable_maps.poly_ring_off is null");
+    }
+    auto positive = [&](const char* field, double v) {
+      if (!(v > 0.0) || !std::isfinite(v))
+        bad(std::string("dd_area_params.") + field + " = " + std::to_string(v) + " must be positive and finite");
+    };
+    positive("half_length", ap->half_length);
+    positive("half_width", ap->half_width);
+    positive("rear_axle_to_center", ap->rear_axle_to_center);
+    positive("dt", ap->dt);
+    check_score_params(bad, *sp);
+    ddmi::launch_collisions(states, areas, N, per_group, *obs, *ix, G, *ap, *sp, work, out_no_collision,
+                            out_collision_time_idx, out_ttc, out_ttc_time_idx, static_cast<hipStream_t>(stream));
+  });
+}
+
+int dd_progress(const double* states, int N, int per_group, const dd_centerlines* lines, int G,
+                const dd_area_params* ap, double* out_raw_progress, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_progress: " + what); };
+    check_counts(bad, N, per_group, G, true);
+    if (!states) bad("states is null");
+    if (!lines) bad("lines is null");
+    if (!ap) bad("area_params is null");
+    if (!out_raw_progress) bad("out_raw_progress is null");
+    if (!lines->verts) bad("dd_centerlines.verts is null");
+    if (!lines->scene_off) bad("dd_centerlines.scene_off is null");
+    if (lines->num_verts < 2 * (long long)G)
+      bad("dd_centerlines.num_verts = " + std::to_string(lines->num_verts) + " is below two per scene");
+    if (!(ap->rear_axle_to_center > 0.0) || !std::isfinite(ap->rear_axle_to_center))
+      bad("dd_area_params.rear_axle_to_center = " + std::to_string(ap->rear_axle_to_center) +
+          " must be positive and finite");
+    ddmi::launch_progress(states, N, per_group, *lines, ap->rear_axle_to_center, out_raw_progress,
+                          static_cast<hipStream_t>(stream));
+  });
+}
+
+int dd_pdm_aggregate(const double* no_collision, const double* drivable_area, const double* driving_direction,
+                     const double* raw_progress, const double* ttc, const uint8_t* comfort, int N, int per_group,
+                     const dd_score_params* sp, const double* progress_reference, double* out_score,
+                     double* out_progress, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_pdm_aggregate: " + what); };
+    check_counts(bad, N, per_group, 0, false);
+    if (!no_collision) bad("no_collision is null");
+    if (!drivable_area) bad("drivable_area is null");
+    if (!driving_direction) bad("driving_direction is null");
+    if (!raw_progress) bad("raw_progress is null");
+    if (!ttc) bad("ttc is null");
+    if (!comfort) bad("comfort is null");
+    if (!sp) bad("score_params is null");
+    if (!out_score) bad("out_score is null");
+    if (!out_progress) bad("out_progress is null");
+    check_score_params(bad, *sp);
+    ddmi::launch_pdm_aggregate(no_collision, drivable_area, driving_direction, raw_progress, ttc, comfort, N,
+                               per_group, *sp, progress_reference, out_score, out_progress,
+                               static_cast<hipStream_t>(stream));
   });
 }
 

@@ -8,8 +8,12 @@ samples outputs (B, S, 20, 8, 3), read in place - in float64 as the reference do
 on the device (``dd_comfort``: the six flags of ``ego_is_comfortable``, pdm_comfort_metrics.py:313-336), and
 ``ego_areas`` the map flags of every state with the drivable-area and driving-direction compliance scores
 (``dd_ego_areas``: ``PDMScorer._calculate_ego_area``, pdm_scorer.py:240-291, 351-396) against maps packed once by
-``pack_drivable_maps``. Collision, progress and TTC need the observations and the centerline as well and are out of
-scope. There is no CPU fallback: a missing library or device raises.
+``pack_drivable_maps``. ``collisions`` scores no-at-fault collision and time-to-collision against the tracked objects
+packed by ``pack_observations`` (``dd_collisions``: :293-349 and :414-498), ``progress`` the raw progress along the
+centerlines packed by ``pack_centerlines`` (``dd_progress``: :398-412), ``aggregate`` combines the sub-scores
+(``dd_pdm_aggregate``: ``_aggregate_scores``, :156-183), and ``pdm_score`` chains all of it on one stream, so that
+candidates are ranked by PDM score without leaving the device. There is no CPU fallback: a missing library or device
+raises.
 """
 import ctypes
 from typing import Mapping, NamedTuple, Optional, Sequence, Tuple, Union
@@ -222,7 +226,7 @@ def _scene_items(entry):
     return list(entry)
 
 
-def pack_drivable_maps(maps: Sequence, device) -> PackedDrivableMaps:
+def pack_drivable_maps(maps: Sequence, device, layers: Optional[Sequence[str]] = None) -> PackedDrivableMaps:
     """The maps of G scenes -> the flat tensors ``dd_ego_areas`` reads, on ``device``. ``maps`` has one entry per
     scene: a list of ``(rings, layer, on_route)`` items - ``rings`` the polygon's rings, exterior first, each an (n, 2)
     sequence of x, y whose closing edge is implied (a repeated closing vertex is harmless); ``layer`` one of the
@@ -230,9 +234,15 @@ def pack_drivable_maps(maps: Sequence, device) -> PackedDrivableMaps:
     polygon's token is among the route's lane ids - or a duck-typed ``PDMDrivableMap``, read only through
     ``_geometries[i].exterior.coords`` / ``.interiors``, ``map_types[i].name`` and ``tokens``, given as
     ``(drivable_map, route_lane_ids)`` or carrying a ``route_lane_ids`` attribute. A scene may have no polygons.
-    Raises ``ValueError`` on a ring with fewer than 3 vertices, a non-finite vertex or an unknown layer name: the
-    device trusts these arrays."""
+    ``layers``: keep only the polygons whose layer name is among these (``("INTERSECTION",)`` is what
+    ``collisions`` reads); None keeps all. Raises ``ValueError`` on a ring with fewer than 3 vertices, a non-finite
+    vertex or an unknown layer name: the device trusts these arrays."""
     verts, ring_off, poly_ring_off, kinds, scene_poly_off = [], [0], [0], [], [0]
+    if layers is not None:
+        layers = set(layers)
+        unknown = layers - set(LAYER_KINDS)
+        if unknown:
+            raise ValueError(f"unknown layer names {sorted(unknown)} (known: {sorted(LAYER_KINDS)})")
     nv = 0
     for g, entry in enumerate(maps):
         for i, item in enumerate(_scene_items(entry)):
@@ -243,6 +253,8 @@ def pack_drivable_maps(maps: Sequence, device) -> PackedDrivableMaps:
             name = getattr(layer, "name", layer)
             if name not in LAYER_KINDS:
                 raise ValueError(f"scene {g} polygon {i}: unknown layer name {name!r} (known: {sorted(LAYER_KINDS)})")
+            if layers is not None and name not in layers:
+                continue
             kind = LAYER_KINDS[name]
             if on_route and kind == KIND_LANE:
                 kind |= KIND_ON_ROUTE
@@ -344,3 +356,389 @@ def ego_areas(states: torch.Tensor, maps, params=None, coords: bool = False,
         raise ValueError((lib.dd_last_error() or b"").decode(errors="replace"))
     _lib.check(rc, lib)
     return EgoAreas(areas.view(torch.bool), scores[..., 0], scores[..., 1], progress, pts)
+
+
+# ---- the rest of the score (dd_collisions, dd_progress, dd_pdm_aggregate): collisions, TTC, progress, aggregation
+
+MIN_OBS_TIMES = 50            # TTC reads occupancy map t + 9 for t up to 40
+RED_LIGHT_TOKEN = "red_light"  # PDMObservation.red_light_token: such tokens never count
+AGENT_TYPE_NAMES = ("VEHICLE", "PEDESTRIAN", "BICYCLE")   # nuPlan's AGENT_TYPES, quoted from memory (include/ddmi.h)
+TRACK_STOPPED_SPEED = 5e-2    # nuPlan's is_track_stopped, quoted from memory
+FLAG_STOPPED, FLAG_AGENT = 1, 2   # dd_observations.flags
+
+
+class PackedObservations(NamedTuple):
+    """``dd_observations``: the tracked objects of G scenes as flat device tensors (include/ddmi.h)."""
+    boxes: torch.Tensor            # float64 (K, T_obs, 4, 2): front-left, rear-left, rear-right, front-right
+    valid: torch.Tensor            # uint8 (K, T_obs)
+    heading: torch.Tensor          # float64 (K)
+    flags: torch.Tensor            # uint8 (K): bit 0 stopped, bit 1 agent type
+    scene_track_off: torch.Tensor  # int32 (G + 1)
+    tokens: Tuple[Tuple[str, ...], ...]   # per scene, the packed tracks' tokens in order (host only)
+
+
+class PackedCenterlines(NamedTuple):
+    """``dd_centerlines``: the centerlines of G scenes as flat device tensors (include/ddmi.h)."""
+    verts: torch.Tensor       # float64 (V, 2)
+    scene_off: torch.Tensor   # int32 (G + 1)
+
+
+class Collisions(NamedTuple):
+    no_collision: torch.Tensor         # float64 (...): 1, 0.5 or 0
+    collision_time_idx: torch.Tensor   # float64 (...): the first at-fault time index, inf if none
+    ttc: torch.Tensor                  # float64 (...): 1 or 0
+    ttc_time_idx: torch.Tensor         # float64 (...): the first TTC infraction's time index, inf if none
+
+
+class PDMScores(NamedTuple):
+    no_collision: torch.Tensor         # float64 (...): 1, 0.5 or 0
+    drivable_area: torch.Tensor        # float64 (...): 1 or 0
+    driving_direction: torch.Tensor    # float64 (...): 1, 0.5 or 0
+    progress: torch.Tensor             # float64 (...): the normalised progress term
+    ttc: torch.Tensor                  # float64 (...): 1 or 0
+    comfort: torch.Tensor              # bool (..., 6)
+    collision_time_idx: torch.Tensor   # float64 (...)
+    ttc_time_idx: torch.Tensor         # float64 (...)
+    raw_progress: torch.Tensor         # float64 (...): metres along the centerline
+    score: torch.Tensor                # float64 (...)
+
+
+def _quad(coords, what):
+    a = np.asarray(coords, dtype=np.float64)
+    if a.ndim == 2 and a.shape == (5, 2):
+        a = a[:4]   # shapely's closed ring
+    if a.shape != (4, 2):
+        raise ValueError(f"{what}: a box is 4 (or 5, closed) x 2 coordinates, got {a.shape}")
+    return a
+
+
+def _scene_tracks(entry, g):
+    """One scene's tracks as (token, boxes (T_obs, 4, 2), valid (T_obs), heading, is_agent, is_stopped), the red-light
+    and previously collided tokens dropped."""
+    out, seen = [], set()
+    if hasattr(entry, "_occupancy_maps"):
+        maps, skip = entry._occupancy_maps, set(entry.collided_track_ids)
+        t_obs = len(maps)
+        per = {}
+        for t, m in enumerate(maps):
+            if len(set(m.tokens)) != len(m.tokens):
+                raise ValueError(f"scene {g} map {t}: duplicate token")
+            for i, token in enumerate(m.tokens):
+                if RED_LIGHT_TOKEN in token or token in skip:
+                    continue
+                if token not in per:
+                    per[token] = (np.zeros((t_obs, 4, 2)), np.zeros(t_obs, dtype=bool))
+                per[token][0][t] = _quad(m._geometries[i].exterior.coords, f"scene {g} map {t} token {token!r}")
+                per[token][1][t] = True
+        for token, (boxes, valid) in per.items():
+            obj = entry.unique_objects[token]
+            is_agent = obj.tracked_object_type.name in AGENT_TYPE_NAMES
+            velocity = getattr(obj, "velocity", None)
+            # is_track_stopped: not an Agent (no velocity), or an Agent at or below 5e-2 m/s
+            stopped = velocity is None or float(velocity.magnitude()) <= TRACK_STOPPED_SPEED
+            out.append((token, boxes, valid, float(obj.box.center.heading), is_agent, stopped))
+        return out, t_obs
+    t_obs = None
+    for i, item in enumerate(entry):
+        try:
+            token, boxes, heading, is_agent, is_stopped = item
+        except (TypeError, ValueError):
+            raise ValueError(f"scene {g} track {i}: expected (token, boxes, heading, is_agent, is_stopped)") from None
+        mask = None
+        if isinstance(boxes, tuple):
+            boxes, mask = boxes
+        b = np.asarray(boxes, dtype=np.float64)
+        if b.ndim == 3 and b.shape[1:] == (5, 2):
+            b = b[:, :4]
+        if b.ndim != 3 or b.shape[1:] != (4, 2):
+            raise ValueError(f"scene {g} track {i}: boxes are (T_obs, 4 (or 5, closed), 2), got {b.shape}")
+        valid = ~np.isnan(b).all(axis=(1, 2)) if mask is None else np.asarray(mask, dtype=bool)
+        if valid.shape != (b.shape[0],):
+            raise ValueError(f"scene {g} track {i}: the mask has shape {valid.shape} for {b.shape[0]} times")
+        if t_obs is None:
+            t_obs = b.shape[0]
+        elif t_obs != b.shape[0]:
+            raise ValueError(f"scene {g} track {i}: {b.shape[0]} times, the tracks before it {t_obs}")
+        if token in seen:
+            raise ValueError(f"scene {g} track {i}: duplicate token {token!r}")
+        seen.add(token)
+        if RED_LIGHT_TOKEN in token:
+            continue
+        out.append((token, np.where(valid[:, None, None], b, 0.0), valid, float(heading), bool(is_agent),
+                    bool(is_stopped)))
+    return out, t_obs
+
+
+def pack_observations(observations: Sequence, device, collided: Optional[Sequence] = None) -> PackedObservations:
+    """The tracked objects of G scenes -> the flat tensors ``dd_collisions`` reads, on ``device``. One entry per scene:
+    a list of ``(token, boxes, heading, is_agent, is_stopped)`` - ``boxes`` (T_obs, 4, 2) float64, corners front-left,
+    rear-left, rear-right, front-right, an all-NaN row where the object is absent, or ``(boxes, mask)`` with a
+    (T_obs) bool mask of presence; ``heading`` the object's heading at its first appearance - or a duck-typed
+    ``PDMObservation``, read only through ``_occupancy_maps[t].tokens`` / ``._geometries[i].exterior.coords``,
+    ``collided_track_ids`` and ``unique_objects[token].box.center.heading`` / ``.tracked_object_type.name`` /
+    ``.velocity.magnitude()`` where present (an object without a velocity is not an Agent and counts as stopped).
+    ``collided[g]``: the list form's ``collided_track_ids``. Tokens containing "red_light" and tokens in the collided
+    ids are DROPPED: both metrics skip them unconditionally. Raises ``ValueError`` on a box that is not 4 (or 5,
+    closed) x 2, a non-finite box where the object is present, fewer than 50 times, scenes that disagree on T_obs, or
+    a duplicate token: the device trusts these arrays."""
+    boxes, valid, heading, flags, off, tokens = [], [], [], [], [0], []
+    t_obs = None
+    for g, entry in enumerate(observations):
+        tracks, t_scene = _scene_tracks(entry, g)
+        skip = set(collided[g]) if collided is not None and not hasattr(entry, "_occupancy_maps") else set()
+        if t_scene is not None:
+            if t_scene < MIN_OBS_TIMES:
+                raise ValueError(f"scene {g}: T_obs = {t_scene} is below {MIN_OBS_TIMES} (TTC reads map t + 9)")
+            if t_obs is not None and t_obs != t_scene:
+                raise ValueError(f"scene {g}: T_obs = {t_scene}, the scenes before it {t_obs}")
+            t_obs = t_scene
+        names = []
+        for token, b, v, h, is_agent, stopped in tracks:
+            if token in skip:
+                continue
+            if not np.isfinite(b[v]).all():
+                raise ValueError(f"scene {g} token {token!r}: non-finite box where the object is present")
+            if not np.isfinite(h):
+                raise ValueError(f"scene {g} token {token!r}: non-finite heading")
+            boxes.append(b), valid.append(v), heading.append(h), names.append(token)
+            flags.append((FLAG_STOPPED if stopped else 0) | (FLAG_AGENT if is_agent else 0))
+        off.append(len(heading))
+        tokens.append(tuple(names))
+    t_obs = t_obs if t_obs is not None else MIN_OBS_TIMES
+    dev = torch.device(device)
+    k = len(heading)
+    if k * t_obs * 8 >= 2 ** 31:
+        raise ValueError(f"{k} tracks x {t_obs} times do not fit the int32 offsets")
+    b = np.stack(boxes) if k else np.zeros((0, t_obs, 4, 2))
+    v = np.stack(valid).astype(np.uint8) if k else np.zeros((0, t_obs), dtype=np.uint8)
+    return PackedObservations(torch.from_numpy(np.ascontiguousarray(b)).to(dev), torch.from_numpy(v).to(dev),
+                              torch.from_numpy(np.asarray(heading, dtype=np.float64)).to(dev),
+                              torch.from_numpy(np.asarray(flags, dtype=np.uint8)).to(dev),
+                              torch.from_numpy(np.asarray(off, dtype=np.int32)).to(dev), tuple(tokens))
+
+
+def pack_centerlines(paths: Sequence, device) -> PackedCenterlines:
+    """The centerlines of G scenes -> the flat tensors ``dd_progress`` reads. One entry per scene: an (L, 2) polyline
+    or a duck-typed ``PDMPath``, read through ``_states_se2_array[:, :2]``. Raises ``ValueError`` on fewer than 2
+    vertices or a non-finite vertex."""
+    verts, off = [], [0]
+    for g, path in enumerate(paths):
+        a = np.asarray(path._states_se2_array if hasattr(path, "_states_se2_array") else path, dtype=np.float64)
+        if a.ndim == 2 and a.shape[1] > 2 and hasattr(path, "_states_se2_array"):
+            a = a[:, :2]
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError(f"scene {g}: a centerline is (L, 2) vertices, got {a.shape}")
+        if a.shape[0] < 2:
+            raise ValueError(f"scene {g}: a centerline of {a.shape[0]} vertices, fewer than 2")
+        if not np.isfinite(a).all():
+            raise ValueError(f"scene {g}: non-finite centerline vertex")
+        verts.append(a)
+        off.append(off[-1] + a.shape[0])
+    if off[-1] >= 2 ** 31:
+        raise ValueError(f"{off[-1]} vertices do not fit the int32 offsets")
+    dev = torch.device(device)
+    v = np.concatenate(verts) if verts else np.zeros((0, 2))
+    return PackedCenterlines(torch.from_numpy(np.ascontiguousarray(v)).to(dev),
+                             torch.from_numpy(np.asarray(off, dtype=np.int32)).to(dev))
+
+
+def default_score_params(lib=None) -> _lib.DDScoreParams:
+    """``dd_default_score_params``: the weights 5 / 5 / 2 / 0, the progress threshold 5 m, the stopped speeds 5e-3
+    (TTC) and 5e-2 (collision) and the ahead / behind bounds of 30 and 150 degrees."""
+    p = _lib.DDScoreParams()
+    (lib or _lib.load()).dd_default_score_params(ctypes.byref(p))
+    return p
+
+
+def _score_params(params: Union[None, _lib.DDScoreParams, Mapping], lib) -> _lib.DDScoreParams:
+    if isinstance(params, _lib.DDScoreParams):
+        return params
+    p = default_score_params(lib)
+    for k, v in (params or {}).items():
+        if k not in dict(p._fields_):
+            raise ValueError(f"unknown score parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def _states_arg(states, lead_dims):
+    if not isinstance(states, torch.Tensor) or states.device.type != "cuda":
+        raise ValueError("states must be a device tensor (simulate_trajectories' / simulate_proposals' output)")
+    if (states.dtype != torch.float64 or states.dim() < 2 + lead_dims
+            or tuple(states.shape[-2:]) != (NUM_STATES, STATE_SIZE)):
+        raise ValueError(f"states must be float64 (B, ..., {NUM_STATES}, {STATE_SIZE}), got {tuple(states.shape)} "
+                         f"{states.dtype}")
+    states = states.contiguous()
+    lead = tuple(states.shape[:-2])
+    n = 1
+    for d in lead:
+        n *= d
+    return states, lead, n
+
+
+def _fields_on(packed, want, dev, name):
+    for field, t, dt in zip(packed._fields, packed, want):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name}.{field} must be a contiguous {dt} tensor on {dev}")
+
+
+def _raise(rc, lib):
+    if rc == -1:  # DD_ERR_INVALID
+        raise ValueError((lib.dd_last_error() or b"").decode(errors="replace"))
+    _lib.check(rc, lib)
+
+
+def collisions(states: torch.Tensor, areas: torch.Tensor, observations, intersections, area_params=None,
+               score_params=None, stream: Optional[torch.cuda.Stream] = None) -> Collisions:
+    """No-at-fault collision and time-to-collision (pdm_scorer.py:293-349, 414-498) on the device. ``states``: device
+    float64 (B, ..., 41, 11); ``areas``: ``ego_areas(states, maps).areas`` (bool or uint8 (B, ..., 41, 3));
+    ``observations``: ``pack_observations``' result for the B scenes (or what it takes: packed here);
+    ``intersections``: ``pack_drivable_maps(maps, device, layers=("INTERSECTION",))``' result (or maps: filtered and
+    packed here). Returns a ``Collisions`` of four float64 (B, ...) tensors. A bad argument raises ``ValueError`` with
+    ``dd_last_error()``'s text."""
+    lib = _lib.load()
+    states, lead, n = _states_arg(states, 1)
+    dev = states.device
+    if not isinstance(areas, torch.Tensor) or areas.device != dev or areas.dtype not in (torch.bool, torch.uint8) \
+            or tuple(areas.shape) != (*lead, NUM_STATES, NUM_AREAS):
+        raise ValueError(f"areas must be ego_areas' bool or uint8 {(*lead, NUM_STATES, NUM_AREAS)} tensor on {dev}")
+    areas = areas.contiguous().view(torch.uint8)
+    if not isinstance(observations, PackedObservations):
+        observations = pack_observations(observations, dev)
+    if not isinstance(intersections, PackedDrivableMaps):
+        intersections = pack_drivable_maps(intersections, dev, layers=("INTERSECTION",))
+    _fields_on(observations, (torch.float64, torch.uint8, torch.float64, torch.uint8, torch.int32), dev, "observations")
+    _fields_on(intersections, (torch.float64, torch.int32, torch.int32, torch.uint8, torch.int32), dev, "intersections")
+    scenes = int(observations.scene_track_off.numel()) - 1
+    if scenes != lead[0] or int(intersections.scene_poly_off.numel()) - 1 != lead[0]:
+        raise ValueError(f"observations hold {scenes} scenes and intersections "
+                         f"{int(intersections.scene_poly_off.numel()) - 1} for {lead[0]} (the first dimension of states)")
+    per_group = n // lead[0] if lead[0] else 0
+    k = int(observations.heading.numel())
+    b = observations.boxes
+    if b.dim() != 4 or tuple(b.shape[2:]) != (4, 2) or b.shape[0] != k or tuple(observations.valid.shape) != \
+            (k, b.shape[1]) or int(observations.flags.numel()) != k:
+        raise ValueError("observations is not what pack_observations returns: boxes / valid / flags do not fit heading")
+    num_polys = int(intersections.poly_kind.numel())
+    if int(intersections.poly_ring_off.numel()) != num_polys + 1:
+        raise ValueError("intersections is not what pack_drivable_maps returns")
+    ap, sp = _area_params(area_params, lib), _score_params(score_params, lib)
+    o = _lib.DDObservations(b.data_ptr() or None, observations.valid.data_ptr() or None,
+                            observations.heading.data_ptr() or None, observations.flags.data_ptr() or None,
+                            observations.scene_track_off.data_ptr() or None, k, int(b.shape[1]))
+    m = _lib.DDDrivableMaps(intersections.verts.data_ptr() or None, intersections.ring_off.data_ptr() or None,
+                            intersections.poly_ring_off.data_ptr() or None, intersections.poly_kind.data_ptr() or None,
+                            intersections.scene_poly_off.data_ptr() or None, num_polys)
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):  # the outputs and the scratch belong to the stream that runs
+        out = torch.empty((4, *lead), dtype=torch.float64, device=dev)
+        work = torch.empty((lib.dd_collisions_work(k),), dtype=torch.float64, device=dev)
+        rc = lib.dd_collisions(states.data_ptr(), areas.data_ptr(), n, per_group, ctypes.byref(o), ctypes.byref(m),
+                               scenes, ctypes.byref(ap), ctypes.byref(sp), work.data_ptr(), out[0].data_ptr(),
+                               out[1].data_ptr(), out[2].data_ptr(), out[3].data_ptr(), s.cuda_stream)
+    _raise(rc, lib)
+    return Collisions(out[0], out[1], out[2], out[3])
+
+
+def progress(states: torch.Tensor, centerlines, area_params=None,
+             stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Raw progress along the centerline (pdm_scorer.py:398-412) on the device: ``states`` device float64
+    (B, ..., 41, 11), ``centerlines`` ``pack_centerlines``' result for the B scenes (or what it takes) -> float64
+    (B, ...) metres, clipped at 0. A bad argument raises ``ValueError`` with ``dd_last_error()``'s text."""
+    lib = _lib.load()
+    states, lead, n = _states_arg(states, 1)
+    dev = states.device
+    if not isinstance(centerlines, PackedCenterlines):
+        centerlines = pack_centerlines(centerlines, dev)
+    _fields_on(centerlines, (torch.float64, torch.int32), dev, "centerlines")
+    scenes = int(centerlines.scene_off.numel()) - 1
+    if scenes != lead[0]:
+        raise ValueError(f"centerlines holds {scenes} scenes for {lead[0]} (the first dimension of states)")
+    per_group = n // lead[0] if lead[0] else 0
+    ap = _area_params(area_params, lib)
+    c = _lib.DDCenterlines(centerlines.verts.data_ptr() or None, centerlines.scene_off.data_ptr() or None,
+                           int(centerlines.verts.numel()) // 2)
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        out = torch.empty(lead, dtype=torch.float64, device=dev)
+        rc = lib.dd_progress(states.data_ptr(), n, per_group, ctypes.byref(c), scenes, ctypes.byref(ap),
+                             out.data_ptr(), s.cuda_stream)
+    _raise(rc, lib)
+    return out
+
+
+def aggregate(no_collision: torch.Tensor, drivable_area: torch.Tensor, driving_direction: torch.Tensor,
+              raw_progress: torch.Tensor, ttc: torch.Tensor, comfort: torch.Tensor, score_params=None,
+              progress_reference: Optional[torch.Tensor] = None,
+              stream: Optional[torch.cuda.Stream] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``PDMScorer._aggregate_scores`` (pdm_scorer.py:156-183) on the device. The five float64 (B, ...) sub-scores and
+    ``comfort`` (B, ..., 6) bool or uint8 -> ``(score, progress)``, both float64 (B, ...). The progress term is
+    normalised by the largest ``raw_progress * no_collision * drivable_area`` of scene b's candidates
+    (``score_proposals``' rule), or, with ``progress_reference`` (B) float64, per candidate by the larger of its own
+    and the scene's reference value - the rule of navsim/evaluate/pdm_score.py:99-130, which scores each prediction as
+    a pair with the PDM-closed trajectory, whose ``raw * multi`` is the reference."""
+    lib = _lib.load()
+    dev = no_collision.device if isinstance(no_collision, torch.Tensor) else None
+    lead = tuple(no_collision.shape) if dev is not None else ()
+    if dev is None or dev.type != "cuda" or len(lead) < 1:
+        raise ValueError("no_collision must be a device tensor (B, ...)")
+    ins = []
+    for name, t in (("no_collision", no_collision), ("drivable_area", drivable_area),
+                    ("driving_direction", driving_direction), ("raw_progress", raw_progress), ("ttc", ttc)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != lead:
+            raise ValueError(f"{name} must be a float64 {lead} tensor on {dev}")
+        ins.append(t.contiguous())
+    if not isinstance(comfort, torch.Tensor) or comfort.device != dev or comfort.dtype not in (torch.bool, torch.uint8) \
+            or tuple(comfort.shape) != (*lead, NUM_COMFORT):
+        raise ValueError(f"comfort must be a bool or uint8 {(*lead, NUM_COMFORT)} tensor on {dev}")
+    comfort = comfort.contiguous().view(torch.uint8)
+    n = 1
+    for d in lead:
+        n *= d
+    per_group = n // lead[0] if lead[0] else 0
+    if progress_reference is not None:
+        if not isinstance(progress_reference, torch.Tensor) or progress_reference.dtype != torch.float64 \
+                or tuple(progress_reference.shape) != (lead[0],):
+            raise ValueError(f"progress_reference must be a float64 ({lead[0]},) tensor")
+        progress_reference = progress_reference.to(dev).contiguous()
+    sp = _score_params(score_params, lib)
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        out = torch.empty((2, *lead), dtype=torch.float64, device=dev)
+        rc = lib.dd_pdm_aggregate(*(t.data_ptr() for t in ins), comfort.data_ptr(), n, per_group, ctypes.byref(sp),
+                                  progress_reference.data_ptr() if progress_reference is not None else None,
+                                  out[0].data_ptr(), out[1].data_ptr(), s.cuda_stream)
+    _raise(rc, lib)
+    return out[0], out[1]
+
+
+def pdm_score(states: torch.Tensor, maps, observations, centerlines, *, progress_reference=None, comfort_params=None,
+              area_params=None, score_params=None, stream: Optional[torch.cuda.Stream] = None) -> PDMScores:
+    """The PDM score of simulated candidates, all on the device and on one stream: ``comfort_metrics``, ``ego_areas``,
+    ``collisions``, ``progress`` and ``aggregate``. ``states``: device float64 (B, ..., 41, 11); ``maps``: the B
+    scenes' maps as ``pack_drivable_maps`` takes them (a ``PackedDrivableMaps`` serves the flags, but the TTC rule
+    needs the INTERSECTION polygons alone: then pass ``(packed_all, packed_intersections)``); ``observations`` and
+    ``centerlines``: packed or as the packers take them. Returns a ``PDMScores`` with the leading shape of
+    ``states``."""
+    states, lead, _ = _states_arg(states, 1)
+    dev = states.device
+    if isinstance(maps, tuple) and len(maps) == 2 and all(isinstance(m, PackedDrivableMaps) for m in maps):
+        packed, inter = maps
+    elif isinstance(maps, PackedDrivableMaps):
+        raise ValueError("pdm_score needs the INTERSECTION polygons on their own: pass the maps themselves, or "
+                         "(pack_drivable_maps(maps, device), pack_drivable_maps(maps, device, layers=('INTERSECTION',)))")
+    else:
+        packed, inter = pack_drivable_maps(maps, dev), pack_drivable_maps(maps, dev, layers=("INTERSECTION",))
+    if not isinstance(observations, PackedObservations):
+        observations = pack_observations(observations, dev)
+    if not isinstance(centerlines, PackedCenterlines):
+        centerlines = pack_centerlines(centerlines, dev)
+    s = stream or torch.cuda.current_stream(dev)
+    comfort = comfort_metrics(states, comfort_params, stream=s)
+    ego = ego_areas(states, packed, area_params, stream=s)
+    col = collisions(states, ego.areas, observations, inter, area_params, score_params, stream=s)
+    raw = progress(states, centerlines, area_params, stream=s)
+    score, term = aggregate(col.no_collision, ego.drivable_area.contiguous(), ego.driving_direction.contiguous(), raw,
+                            col.ttc, comfort, score_params, progress_reference, stream=s)
+    return PDMScores(col.no_collision, ego.drivable_area, ego.driving_direction, term, col.ttc, comfort,
+                     col.collision_time_idx, col.ttc_time_idx, raw, score)

@@ -32,6 +32,10 @@
  *   dd_ego_areas <- PDMScorer._calculate_ego_area, _calculate_drivable_area_compliance and
  *                  _calculate_driving_direction_compliance      pdm_planner/scoring/pdm_scorer.py:240-291,351-396
  *                  (the three map flags of every simulated state and the two scores that need nothing else)
+ *   dd_collisions <- PDMScorer._calculate_no_at_fault_collision, get_collision_type and _calculate_ttc
+ *                  pdm_scorer.py:293-349,414-498, pdm_scorer_utils.py:13-65
+ *   dd_progress  <- PDMScorer._calculate_progress               pdm_scorer.py:398-412
+ *   dd_pdm_aggregate <- PDMScorer._aggregate_scores             pdm_scorer.py:156-183
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
  * handle must be serialised by the caller (the reference runs one agent per worker process,
@@ -307,8 +311,8 @@ int dd_tap(dd_handle* h, const char* name, float* dst, size_t count, size_t* act
  * candidates (dd_forward_samples draws up to 32 x 20 per scene) without a handle, in float64 throughout as the
  * reference does, deterministically (no atomics; two calls on the same input are bit-equal). Of the sub-scores, comfort
  * is in scope (dd_comfort below: it needs nothing but the states), and so are drivable-area and driving-direction
- * compliance (dd_ego_areas below: the states and the scene's map polygons); collision, progress and TTC need the
- * observations and the centerline as well and are out of scope. */
+ * compliance (dd_ego_areas below: the states and the scene's map polygons); collision and TTC (dd_collisions: the
+ * tracked objects as well), progress (dd_progress: the centerline) and the aggregation (dd_pdm_aggregate) follow. */
 typedef struct dd_sim_params {
   double wheel_base;                /* 3.089 m (nuPlan's get_pacifica_parameters) */
   double dt;                        /* 0.1 s: the proposal's sampling interval and the tracker's discretisation; the
@@ -470,6 +474,105 @@ size_t dd_ego_areas_work(int P);
 int dd_ego_areas(const double* states, int N, int per_group, const dd_drivable_maps* maps, int G,
                  const dd_area_params* params, double* work, uint8_t* out_areas, double* out_scores,
                  double* out_progress, double* out_coords, void* stream);
+
+/* ---- the rest of the PDM score: no-at-fault collision and time-to-collision (PDMScorer._calculate_no_at_fault_collision
+ * :293-349 with get_collision_type, pdm_scorer_utils.py:13-65, and _calculate_ttc :414-498), progress along the
+ * centerline (:398-412) and the aggregation (_aggregate_scores :156-183), on the GPU ---- */
+/* The weights and thresholds of PDMScorerConfig (:36-58), get_collision_type's stopped-speed default, and the two angle
+ * bounds of nuPlan's is_agent_ahead / is_agent_behind (observation/idm/utils.py), which are quoted from memory of
+ * nuPlan - it is not part of this tree - and are parameters for that reason:
+ *   angle = arccos(dot((cos h, sin h), (track - ego) / |track - ego|)); ahead: angle < ahead_angle; behind: angle >
+ *   behind_angle; a zero-length vector, or a dot product rounded past 1, gives NaN and both are false.
+ * The TTC look-ahead steps are fixed at {0, 3, 6, 9} (np.arange(0, 10, 3), :426). */
+typedef struct dd_score_params {
+  double progress_weight;                    /* 5 */
+  double ttc_weight;                         /* 5 */
+  double comfortable_weight;                 /* 2 */
+  double driving_direction_weight;           /* 0 */
+  double progress_distance_threshold;        /* 5.0 m */
+  double ttc_stopped_speed_threshold;        /* 5e-3 m/s: below it a state takes no part in TTC */
+  double collision_stopped_speed_threshold;  /* 5e-2 m/s: at or below it the ego is stopped (STOPPED_EGO) */
+  double ahead_angle;                        /* deg2rad(30) */
+  double behind_angle;                       /* deg2rad(150) */
+} dd_score_params;
+/* Fill *p with the values listed above. */
+void dd_default_score_params(dd_score_params* p);
+/* The tracked objects of G scenes as flat device arrays, track-major. A track is one object over T_obs occupancy maps;
+ * it need not exist at every time (valid), and a NaN box never stands for absence. Every valid box must be finite and
+ * CONVEX (nuPlan's oriented boxes are rectangles), corners in the order front-left, rear-left, rear-right, front-right
+ * (either orientation). Tracks whose token contains "red_light" and tracks in collided_track_ids are skipped by both
+ * metrics unconditionally and are not packed at all. The arrays are TRUSTED, not validated:
+ * diffusiondrive_amd.simulate.pack_observations guarantees them. */
+typedef struct dd_observations {
+  const double* boxes;             /* device double (K, T_obs, 4, 2) */
+  const uint8_t* valid;            /* device uint8 (K, T_obs): 1 where the track is in occupancy map t */
+  const double* heading;           /* device double (K): unique_objects[token].box.center.heading (the first appearance):
+                                      the reference's track state carries it, the angle rule as quoted reads only the
+                                      centroid, and dd_collisions does not read it */
+  const uint8_t* flags;            /* device uint8 (K): bit 0 stopped (is_track_stopped: not an Agent, or speed <= 5e-2),
+                                      bit 1 agent type (VEHICLE, PEDESTRIAN, BICYCLE: an at-fault hit scores 0, else 0.5) */
+  const int32_t* scene_track_off;  /* device int32 (G + 1): scene g = tracks scene_track_off[g] .. [g + 1] - 1 */
+  int num_tracks;                  /* K, the host's copy of scene_track_off[G]; with K = 0 the first four may be NULL */
+  int num_times;                   /* T_obs >= 50: TTC reads map t + 9 for t up to 40 */
+} dd_observations;
+/* The centerlines of G scenes: scene g's polyline is vertices scene_off[g] .. scene_off[g + 1] - 1, at least 2, all
+ * finite (TRUSTED; simulate.pack_centerlines guarantees it). */
+typedef struct dd_centerlines {
+  const double* verts;        /* device double (V, 2) */
+  const int32_t* scene_off;   /* device int32 (G + 1) */
+  int num_verts;              /* V, the host's copy of scene_off[G]; at least 2 G */
+} dd_centerlines;
+/* Device scratch of dd_collisions over K tracks, in doubles (each track's bounding box over its valid times). Never 0. */
+size_t dd_collisions_work(int K);
+/* states (N, 41, 11) and areas (N, 41, 3) exactly as dd_simulate and dd_ego_areas write them; candidate n meets the
+ * tracks of scene n / per_group. intersections: the polygons of layer INTERSECTION only (pack_drivable_maps(...,
+ * layers=("INTERSECTION",)); poly_kind is not read; a scene may have none). The ego quad is the four corners of
+ * dd_ego_areas; the TTC quads are those corners + (cos h, sin h) * hypot(vx, vy) * (double(k) * dt), k = 0, 3, 6, 9,
+ * tested against map t + k. Two quads intersect when they share a point (closed: touching counts), by a separating-
+ * axis test over differences against an ego corner; a quad with a non-finite corner intersects nothing (this
+ * project's rule: shapely raises or answers per GEOS build). The centroid is the area centroid (the corner mean for a
+ * zero-area box). Per (candidate, track) only the first hit decides:
+ *   collision: the first t with an intersection. speed <= collision_stopped_speed_threshold: not at fault; else a
+ *     stopped track: at fault; else the track's centroid at t (with `heading`) behind the rear-axle pose: not at fault;
+ *     else the segment front-left - front-right intersects the box: at fault; else (lateral) at fault iff areas[n, t]
+ *     has multiple-lanes or non-drivable set. At fault: no_collision = min(., agent ? 0 : 0.5), time index min(., t).
+ *   TTC: the first (t, k) in lexicographic order with an intersection and NOT speed[t] < ttc_stopped_speed_threshold.
+ *     Infraction (ttc = 0, time index min(., t)) iff the centroid at t + k is ahead, or it is not behind and either
+ *     flag is set at t or the rear-axle point (x, y) is strictly inside an INTERSECTION polygon (the containment rule
+ *     of dd_ego_areas).
+ * Outputs, device double (N) each: no_collision in {1, 0.5, 0}, collision_time_idx (inf if none), ttc in {1, 0},
+ * ttc_time_idx (inf if none). Two launches on `stream` (the tracks' bounding boxes, then one candidate per
+ * wavefront); no allocation, copy, synchronisation or atomics: two calls are bit-equal. DD_ERR_INVALID before any
+ * device work, naming the argument or field in dd_last_error(): N <= 0, per_group <= 0, N % per_group != 0, G != N /
+ * per_group, a null states / areas / obs / intersections / area_params / score_params / work / output, null
+ * scene_track_off or scene_poly_off, num_tracks < 0 or a null observation array with num_tracks > 0, num_times < 50,
+ * num_polys < 0 or a null polygon array with num_polys > 0, a vehicle length or dt that is not positive and finite, a
+ * dd_score_params field that is non-finite or negative, a zero weight sum, ahead_angle > behind_angle. */
+int dd_collisions(const double* states, const uint8_t* areas, int N, int per_group, const dd_observations* obs,
+                  const dd_drivable_maps* intersections, int G, const dd_area_params* area_params,
+                  const dd_score_params* score_params, double* work, double* out_no_collision,
+                  double* out_collision_time_idx, double* out_ttc, double* out_ttc_time_idx, void* stream);
+/* raw progress (N): max(project(center[40]) - project(center[0]), 0) along scene n / per_group's centerline, the center
+ * as in dd_ego_areas. project is shapely's LineString.project as GEOS is remembered to do it (it cannot be run here):
+ * the nearest segment, the FIRST on a tie, the parameter clamped to [0, 1], the lengths of the segments before it
+ * summed in order plus the partial length; differences against the segment's start. A NaN center gives NaN. One
+ * launch, one thread per candidate. DD_ERR_INVALID: the counts as above, null states / lines / params / out, null
+ * lines->verts / scene_off, num_verts < 2 G, a non-positive or non-finite rear_axle_to_center. */
+int dd_progress(const double* states, int N, int per_group, const dd_centerlines* lines, int G,
+                const dd_area_params* area_params, double* out_raw_progress, void* stream);
+/* _aggregate_scores. Inputs device double (N) but comfort, device uint8 (N, 6) as dd_comfort writes it. multi =
+ * no_collision * drivable_area; p = raw_progress * multi; pmax = the NaN-keeping max (np.max) of p over the per_group
+ * candidates of the scene (score_proposals' rule), or with progress_reference (device double (G), else NULL) pmax_n =
+ * np.max([progress_reference[n / per_group], p_n]) (pdm_score.py:99-130 scores the pair [PDM-closed, prediction]: the
+ * reference value is the PDM-closed trajectory's raw * multi). progress = p / pmax if pmax >
+ * progress_distance_threshold, else 1 where multi != 0 and 0 where multi == 0 (a NaN pmax takes this branch). score =
+ * multi * ((((w_p progress + w_t ttc) + w_c all(comfort)) + w_d driving_direction) / (((w_p + w_t) + w_c) + w_d)).
+ * One launch, one workgroup per scene, no atomics. DD_ERR_INVALID: the counts, a null input / params / output, a
+ * dd_score_params field that is non-finite or negative, a zero weight sum. */
+int dd_pdm_aggregate(const double* no_collision, const double* drivable_area, const double* driving_direction,
+                     const double* raw_progress, const double* ttc, const uint8_t* comfort, int N, int per_group,
+                     const dd_score_params* score_params, const double* progress_reference, double* out_score,
+                     double* out_progress, void* stream);
 
 /* ---- input feature builder (TransfuserFeatureBuilder.compute_features on the GPU) ---------- */
 /* Camera feature (transfuser_features.py:57-77): crop + stitch + cv2 INTER_LINEAR resize +
