@@ -189,7 +189,7 @@ def independent_touch(a, b):
 
 def independent_project(line, x, y, per_metre=2000):
     """Arc length of the nearest of dense samples of the polyline, and the bound of its error: the sample spacing
-    plus what a near-tie between two samples can hide."""
+    plus what a near-tie between two samples can hide. x, y: one point (a float comes back) or arrays of points."""
     line = np.asarray(line, dtype=np.float64)
     seg = np.linalg.norm(np.diff(line, axis=0), axis=1)
     cum = np.concatenate([[0.0], np.cumsum(seg)])
@@ -200,8 +200,12 @@ def independent_project(line, x, y, per_metre=2000):
         pts.append(line[i] + f[:, None] * (line[i + 1] - line[i]))
         arc.append(cum[i] + f * length)
     pts, arc = np.concatenate(pts), np.concatenate(arc)
-    j = int(np.argmin((pts[:, 0] - x) ** 2 + (pts[:, 1] - y) ** 2))
-    return float(arc[j]), 1.0 / per_metre
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    out = np.empty(x.size)
+    for at in range(0, x.size, 16):       # the samples against 16 points at a time
+        qx, qy = x.reshape(-1)[at:at + 16], y.reshape(-1)[at:at + 16]
+        out[at:at + 16] = arc[np.argmin((pts[:, :1] - qx) ** 2 + (pts[:, 1:] - qy) ** 2, axis=0)]
+    return (float(out[0]) if x.ndim == 0 else out.reshape(x.shape)), 1.0 / per_metre
 
 
 # ---- the restatement
