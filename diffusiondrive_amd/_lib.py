@@ -126,6 +126,30 @@ class DDCenterlines(ctypes.Structure):
     _fields_ = [("verts", c_void_p), ("scene_off", c_void_p), ("num_verts", ctypes.c_int)]
 
 
+class DDPaths(ctypes.Structure):
+    """dd_paths: the lateral paths of G scenes as flat device arrays (include/ddmi.h)."""
+    _fields_ = [("verts", c_void_p), ("progress", c_void_p), ("path_off", c_void_p),
+                ("paths_per_scene", ctypes.c_int), ("num_verts", ctypes.c_int)]
+
+
+class DDLeadObjects(ctypes.Structure):
+    """dd_lead_objects: the tracks and stop polygons dd_proposals reads (include/ddmi.h)."""
+    _fields_ = [
+        ("boxes", c_void_p), ("valid", c_void_p), ("heading", c_void_p), ("speed", c_void_p),
+        ("scene_track_off", c_void_p), ("num_tracks", ctypes.c_int), ("num_times", ctypes.c_int),
+        ("stop_verts", c_void_p), ("ring_off", c_void_p), ("scene_ring_off", c_void_p), ("num_rings", ctypes.c_int),
+    ]
+
+
+class DDIdmParams(ctypes.Structure):
+    """dd_idm_params: the IDM policy's and the generator's constants (include/ddmi.h)."""
+    _fields_ = [
+        ("min_gap_to_lead_agent", ctypes.c_double), ("headway_time", ctypes.c_double), ("accel_max", ctypes.c_double),
+        ("decel_max", ctypes.c_double), ("dt", ctypes.c_double), ("acceleration_exponent", ctypes.c_int),
+        ("leading_agent_update_rate", ctypes.c_int), ("corridor_poses", ctypes.c_int),
+    ]
+
+
 class DDOpView(ctypes.Structure):
     """dd_op_view: a strided (n, h, w, c) operand of the view-taking single-op entries (include/ddmi.h)."""
     _fields_ = [("p", c_void_p), ("sn", ctypes.c_int64), ("sh", ctypes.c_int64), ("sw", ctypes.c_int64),
@@ -211,6 +235,14 @@ _SIGS = {
     "dd_pdm_aggregate": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
                                         ctypes.c_int, ctypes.POINTER(DDScoreParams), c_void_p, c_void_p, c_void_p,
                                         c_void_p]),
+    "dd_default_idm_params": (None, [ctypes.POINTER(DDIdmParams)]),
+    "dd_proposals_work": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "dd_proposals": (ctypes.c_int, [ctypes.POINTER(DDPaths), ctypes.POINTER(DDLeadObjects), c_void_p, c_void_p,
+                                    c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDIdmParams),
+                                    ctypes.POINTER(DDAreaParams), c_void_p, ctypes.c_size_t, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_void_p]),
+    "dd_pdm_select": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "dd_set_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_set_schedule": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_get_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int)]),

@@ -226,6 +226,17 @@ class DiffusionDriveAgent(_Base):
             states = states.to(torch.device("cuda", self._transfuser_model.device))
         return pdm_score(states, maps, observations, centerlines, **kwargs)
 
+    def pdm_closed_reference(self, paths, lead_objects, ego_states, target_velocities, maps, observations, centerlines,
+                             **kwargs):
+        """The PDM-Closed planner's candidate stage on the GPU (``diffusiondrive_amd.simulate.pdm_closed``): the
+        P x L IDM proposals of every scene (``PDMGenerator.generate_proposals``, pdm_generator.py:68-95), simulated,
+        scored and the best picked. Returns a ``PDMClosed`` whose ``progress_reference`` (B) is what
+        ``pdm_score(progress_reference=)`` takes to score this agent's candidates as pairs with the PDM-Closed
+        trajectory. Host arguments are packed on and moved to the model's device."""
+        from .simulate import pdm_closed
+        return pdm_closed(paths, lead_objects, ego_states, target_velocities, maps, observations, centerlines,
+                          device=torch.device("cuda", self._transfuser_model.device), **kwargs)
+
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).
 TransfuserAgent = DiffusionDriveAgent

@@ -24,6 +24,9 @@ struct dd_drivable_maps;
 struct dd_score_params;
 struct dd_observations;
 struct dd_centerlines;
+struct dd_paths;
+struct dd_lead_objects;
+struct dd_idm_params;
 
 namespace ddmi {
 
@@ -662,5 +665,16 @@ void launch_pdm_aggregate(const double* no_collision, const double* drivable_are
                           const double* raw_progress, const double* ttc, const uint8_t* comfort, int N, int per_group,
                           const dd_score_params& sp, const double* progress_reference, double* out_score,
                           double* out_progress, hipStream_t st);
+
+// ---- proposals.hip: PDM-Closed's proposal generation (dd_proposals) and the pick of the best (dd_pdm_select); work =
+// proposals_work_doubles(G, P, K, R) doubles. The parameters are checked by the caller.
+size_t proposals_work_doubles(int G, int P, int K, int R);
+void launch_proposals(const dd_paths& paths, const dd_lead_objects& obs, const double* ego_states,
+                      const double* targets, int G, int L, const dd_idm_params& ip, const dd_area_params& ap,
+                      double* work, double* out_proposals, double* out_idm, double* out_lead, int32_t* out_lead_index,
+                      hipStream_t st);
+void launch_pdm_select(const double* score, const double* raw_progress, const double* no_collision,
+                       const double* drivable_area, const double* states, int G, int per_group, int32_t* out_index,
+                       double* out_states, double* out_reference, hipStream_t st);
 
 }  // namespace ddmi

@@ -2900,6 +2900,114 @@ int dd_pdm_aggregate(const double* no_collision, const double* drivable_area, co
   });
 }
 
+// ---- PDM-Closed's proposal generation and the pick of the best (proposals.hip): stateless, every argument checked
+// before any device work
+void dd_default_idm_params(dd_idm_params* p) {
+  if (!p) return;
+  p->min_gap_to_lead_agent = 1.0;
+  p->headway_time = 1.5;
+  p->accel_max = 1.5;
+  p->decel_max = 3.0;
+  p->dt = 0.1;
+  p->acceleration_exponent = 10;
+  p->leading_agent_update_rate = 2;
+  p->corridor_poses = 50;
+}
+
+size_t dd_proposals_work(int G, int P, int K, int R) { return ddmi::proposals_work_doubles(G, P, K, R); }
+
+int dd_proposals(const dd_paths* paths, const dd_lead_objects* obs, const double* ego_states, const double* targets,
+                 const double* targets_host, int G, int L, const dd_idm_params* ip, const dd_area_params* ap,
+                 double* work, size_t work_doubles, double* out_proposals, double* out_idm, double* out_lead,
+                 int32_t* out_lead_index, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_proposals: " + what); };
+    if (G <= 0) bad("G = " + std::to_string(G) + " must be positive");
+    if (L < 1 || L > 64) bad("L = " + std::to_string(L) + " must be in 1..64");
+    if (!paths) bad("paths is null");
+    if (!obs) bad("objects is null");
+    if (!ego_states) bad("ego_states is null");
+    if (!targets) bad("targets is null");
+    if (!ip) bad("idm_params is null");
+    if (!ap) bad("area_params is null");
+    if (!work) bad("work is null");
+    if (!out_proposals) bad("out_proposals is null");
+    if (paths->paths_per_scene <= 0)
+      bad("dd_paths.paths_per_scene = " + std::to_string(paths->paths_per_scene) + " must be positive");
+    if (!paths->verts) bad("dd_paths.verts is null");
+    if (!paths->progress) bad("dd_paths.progress is null");
+    if (!paths->path_off) bad("dd_paths.path_off is null");
+    if ((long long)G * paths->paths_per_scene > (1 << 24))
+      bad("G * dd_paths.paths_per_scene = " + std::to_string((long long)G * paths->paths_per_scene) + " is above 2^24");
+    if (paths->num_verts < 2LL * G * paths->paths_per_scene)
+      bad("dd_paths.num_verts = " + std::to_string(paths->num_verts) + " is below two per path");
+    if (!obs->scene_track_off) bad("dd_lead_objects.scene_track_off is null");
+    if (!obs->scene_ring_off) bad("dd_lead_objects.scene_ring_off is null");
+    if (obs->num_tracks < 0) bad("dd_lead_objects.num_tracks = " + std::to_string(obs->num_tracks) + " is negative");
+    if (obs->num_rings < 0) bad("dd_lead_objects.num_rings = " + std::to_string(obs->num_rings) + " is negative");
+    if (obs->num_times < 41)
+      bad("dd_lead_objects.num_times = " + std::to_string(obs->num_times) + " is below 41 (the update at 40 reads map 40)");
+    if (obs->num_tracks > 0) {
+      if (!obs->boxes) bad("dd_lead_objects.boxes is null");
+      if (!obs->valid) bad("dd_lead_objects.valid is null");
+      if (!obs->heading) bad("dd_lead_objects.heading is null");
+      if (!obs->speed) bad("dd_lead_objects.speed is null");
+    }
+    if (obs->num_rings > 0) {
+      if (!obs->stop_verts) bad("dd_lead_objects.stop_verts is null");
+      if (!obs->ring_off) bad("dd_lead_objects.ring_off is null");
+    }
+    auto positive = [&](const char* group, const char* field, double v) {
+      if (!(v > 0.0) || !std::isfinite(v))
+        bad(std::string(group) + "." + field + " = " + std::to_string(v) + " must be positive and finite");
+    };
+    positive("dd_idm_params", "min_gap_to_lead_agent", ip->min_gap_to_lead_agent);
+    positive("dd_idm_params", "headway_time", ip->headway_time);
+    positive("dd_idm_params", "accel_max", ip->accel_max);
+    positive("dd_idm_params", "decel_max", ip->decel_max);
+    positive("dd_idm_params", "dt", ip->dt);
+    if (ip->acceleration_exponent <= 0)
+      bad("dd_idm_params.acceleration_exponent = " + std::to_string(ip->acceleration_exponent) + " must be positive");
+    if (ip->leading_agent_update_rate <= 0 || ip->leading_agent_update_rate > 40)
+      bad("dd_idm_params.leading_agent_update_rate = " + std::to_string(ip->leading_agent_update_rate) +
+          " must be in 1..40");
+    if (ip->corridor_poses <= 0)
+      bad("dd_idm_params.corridor_poses = " + std::to_string(ip->corridor_poses) + " must be positive");
+    positive("dd_area_params", "half_length", ap->half_length);
+    positive("dd_area_params", "half_width", ap->half_width);
+    positive("dd_area_params", "rear_axle_to_center", ap->rear_axle_to_center);
+    if (targets_host)
+      for (long long i = 0; i < (long long)G * L; ++i)
+        if (!(targets_host[i] > 0.0) || !std::isfinite(targets_host[i]))
+          bad("targets[" + std::to_string(i / L) + ", " + std::to_string(i % L) + "] = " +
+              std::to_string(targets_host[i]) + " must be positive and finite");
+    const size_t need = ddmi::proposals_work_doubles(G, paths->paths_per_scene, obs->num_tracks, obs->num_rings);
+    if (work_doubles < need)
+      bad("work_doubles = " + std::to_string(work_doubles) + " is below dd_proposals_work = " + std::to_string(need));
+    ddmi::launch_proposals(*paths, *obs, ego_states, targets, G, L, *ip, *ap, work, out_proposals, out_idm, out_lead,
+                           out_lead_index, static_cast<hipStream_t>(stream));
+  });
+}
+
+int dd_pdm_select(const double* score, const double* raw_progress, const double* no_collision,
+                  const double* drivable_area, const double* states, int N, int per_group, int32_t* out_index,
+                  double* out_states, double* out_reference, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_pdm_select: " + what); };
+    check_counts(bad, N, per_group, 0, false);
+    if (!score) bad("score is null");
+    if (!raw_progress) bad("raw_progress is null");
+    if (!no_collision) bad("no_collision is null");
+    if (!drivable_area) bad("drivable_area is null");
+    if (!states) bad("states is null");
+    if (!out_index) bad("out_index is null");
+    if (!out_states) bad("out_states is null");
+    if (!out_reference) bad("out_reference is null");
+    ddmi::launch_pdm_select(score, raw_progress, no_collision, drivable_area, states, N / per_group, per_group,
+                            out_index, out_states, out_reference, static_cast<hipStream_t>(stream));
+  });
+}
+
 int dd_set_profiling(dd_handle* h, int enable) {
   return guarded([&] {
     if (!h) throw std::invalid_argument("null handle");

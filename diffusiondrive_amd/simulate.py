@@ -742,3 +742,385 @@ def pdm_score(states: torch.Tensor, maps, observations, centerlines, *, progress
                             col.ttc, comfort, score_params, progress_reference, stream=s)
     return PDMScores(col.no_collision, ego.drivable_area, ego.driving_direction, term, col.ttc, comfort,
                      col.collision_time_idx, col.ttc_time_idx, raw, score)
+
+
+# ---- PDM-Closed's proposal generation (dd_proposals) and the planner's pick (dd_pdm_select)
+
+MIN_LEAD_TIMES = 41           # the leader update at time index 40 reads occupancy map 40
+MAX_POLICIES = 64             # one lane per policy of a path
+
+
+class PackedPaths(NamedTuple):
+    """``dd_paths``: the lateral paths of G scenes as flat device tensors (include/ddmi.h)."""
+    verts: torch.Tensor        # float64 (V, 3): x, y, unwrapped heading
+    progress: torch.Tensor     # float64 (V)
+    path_off: torch.Tensor     # int32 (G P + 1)
+    paths_per_scene: int
+
+
+class PackedLeadObjects(NamedTuple):
+    """``dd_lead_objects``: the tracks and stop polygons ``dd_proposals`` reads (include/ddmi.h)."""
+    boxes: torch.Tensor            # float64 (K, T_obs, 4, 2)
+    valid: torch.Tensor            # uint8 (K, T_obs)
+    heading: torch.Tensor          # float64 (K)
+    speed: torch.Tensor            # float64 (K)
+    scene_track_off: torch.Tensor  # int32 (G + 1)
+    stop_verts: torch.Tensor       # float64 (Vs, 2)
+    ring_off: torch.Tensor         # int32 (R + 1)
+    scene_ring_off: torch.Tensor   # int32 (G + 1)
+    tokens: Tuple[Tuple[str, ...], ...]   # per scene, the packed tracks' tokens, then the rings' (host only)
+
+
+class Proposals(NamedTuple):
+    proposals: torch.Tensor              # float64 (G, P L, 41, 3): x, y, heading
+    idm: Optional[torch.Tensor]          # float64 (G, P L, 41, 2): progress, velocity
+    lead: Optional[torch.Tensor]         # float64 (G, P L, 41, 3): the leader's progress, velocity, rear length
+    lead_index: Optional[torch.Tensor]   # int32 (G, P L, 41): object index in the scene (tracks, then rings), -1 free
+
+
+class PDMClosed(NamedTuple):
+    scores: PDMScores                    # of all (G, P L) proposals
+    best_index: torch.Tensor             # int32 (G)
+    best_states: torch.Tensor            # float64 (G, 41, 11)
+    progress_reference: torch.Tensor     # float64 (G): what pdm_score(progress_reference=) takes
+    proposals: torch.Tensor              # float64 (G, P L, 41, 3)
+    states: torch.Tensor                 # float64 (G, P L, 41, 11)
+
+
+def pack_paths(paths: Sequence, device) -> PackedPaths:
+    """The lateral paths of G scenes -> the flat tensors ``dd_proposals`` reads. One entry per scene: a sequence of P
+    paths (the same P in every scene), each a (V, 3) array of x, y, heading - the heading is unwrapped and the
+    cumulative progress formed here as ``PDMPath.__init__`` forms them (np.unwrap; calculate_progress: diff, norm,
+    cumsum) - or a duck-typed ``PDMPath``, read through ``_states_se2_array`` and ``_progress``. Raises ``ValueError``
+    on fewer than 2 vertices, a non-finite value, a progress that decreases, or a length <= 1e-5."""
+    verts, progress, off = [], [], [0]
+    per_scene = None
+    for g, scene in enumerate(paths):
+        scene = list(scene)
+        if per_scene is None:
+            per_scene = len(scene)
+        if len(scene) != per_scene or per_scene == 0:
+            raise ValueError(f"scene {g}: {len(scene)} paths, the scenes before it {per_scene} (at least 1, the same "
+                             "in every scene)")
+        for i, path in enumerate(scene):
+            if hasattr(path, "_states_se2_array"):
+                a = np.array(path._states_se2_array, dtype=np.float64)
+                s = np.array(path._progress, dtype=np.float64)
+            else:
+                a = np.array(path, dtype=np.float64)
+                s = None
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError(f"scene {g} path {i}: a path is (V, 3) x, y, heading, got {a.shape}")
+            if a.shape[0] < 2:
+                raise ValueError(f"scene {g} path {i}: {a.shape[0]} vertices, fewer than 2")
+            if not np.isfinite(a).all():
+                raise ValueError(f"scene {g} path {i}: non-finite value")
+            if s is None:
+                a[:, 2] = np.unwrap(a[:, 2], axis=0)
+                diff = np.concatenate(([np.diff(a[:, 0])], [np.diff(a[:, 1])]), axis=0, dtype=np.float64)
+                s = np.cumsum(np.append(0.0, np.linalg.norm(diff, axis=0)), dtype=np.float64)
+            if s.shape != (a.shape[0],) or not np.isfinite(s).all() or (np.diff(s) < 0.0).any():
+                raise ValueError(f"scene {g} path {i}: the progress must be {a.shape[0]} finite values that never "
+                                 "decrease")
+            if not s[-1] - s[0] > 1e-5 or s[0] != 0.0:
+                raise ValueError(f"scene {g} path {i}: the progress must start at 0 and the length {s[-1] - s[0]} be "
+                                 "above 1e-5")
+            verts.append(a), progress.append(s)
+            off.append(off[-1] + a.shape[0])
+    if per_scene is None:
+        raise ValueError("no scenes")
+    if off[-1] >= 2 ** 31 // 3:
+        raise ValueError(f"{off[-1]} vertices do not fit the int32 offsets")
+    dev = torch.device(device)
+    return PackedPaths(torch.from_numpy(np.ascontiguousarray(np.concatenate(verts))).to(dev),
+                       torch.from_numpy(np.ascontiguousarray(np.concatenate(progress))).to(dev),
+                       torch.from_numpy(np.asarray(off, dtype=np.int32)).to(dev), per_scene)
+
+
+def _ring(coords, what):
+    a = np.asarray(coords, dtype=np.float64)
+    if a.ndim == 2 and a.shape[0] > 1 and a.shape[1] >= 2 and (a[0, :2] == a[-1, :2]).all():
+        a = a[:-1]   # shapely's closed ring
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError(f"{what}: a ring is (n, 2) vertices, got {a.shape}")
+    if a.shape[0] < 3:
+        raise ValueError(f"{what}: {a.shape[0]} vertices, fewer than 3")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what}: non-finite vertex")
+    return a
+
+
+def _scene_lead_objects(entry, g, rings, collided):
+    """One scene's (tracks: (token, boxes, valid, heading, speed)), (rings: (token, (n, 2))), T_obs."""
+    tracks, stops = [], []
+    if hasattr(entry, "_occupancy_maps"):
+        maps, skip = entry._occupancy_maps, set(entry.collided_track_ids)
+        t_obs = len(maps)
+        per = {}
+        for t, m in enumerate(maps):
+            if len(set(m.tokens)) != len(m.tokens):
+                raise ValueError(f"scene {g} map {t}: duplicate token")
+            for i, token in enumerate(m.tokens):
+                if token in skip:
+                    continue
+                if RED_LIGHT_TOKEN in token:   # static over time: the first map that holds it
+                    if token not in per:
+                        per[token] = None
+                        stops.append((token, _ring(m._geometries[i].exterior.coords, f"scene {g} token {token!r}")))
+                    continue
+                if token not in per:
+                    per[token] = (np.zeros((t_obs, 4, 2)), np.zeros(t_obs, dtype=bool))
+                per[token][0][t] = _quad(m._geometries[i].exterior.coords, f"scene {g} map {t} token {token!r}")
+                per[token][1][t] = True
+        for token, pair in per.items():
+            if pair is None:
+                continue
+            obj = entry.unique_objects[token]
+            velocity = getattr(obj, "velocity", None)   # an object without a velocity is no nuPlan Agent
+            tracks.append((token, pair[0], pair[1], float(obj.box.center.heading),
+                           0.0 if velocity is None else float(velocity.magnitude())))
+        return tracks, stops, t_obs
+    t_obs, seen = None, set()
+    for i, item in enumerate(entry):
+        try:
+            token, boxes, heading, _, _, speed = item
+        except (TypeError, ValueError):
+            raise ValueError(f"scene {g} track {i}: expected (token, boxes, heading, is_agent, is_stopped, speed)") \
+                from None
+        mask = None
+        if isinstance(boxes, tuple):
+            boxes, mask = boxes
+        b = np.asarray(boxes, dtype=np.float64)
+        if b.ndim == 3 and b.shape[1:] == (5, 2):
+            b = b[:, :4]
+        if b.ndim != 3 or b.shape[1:] != (4, 2):
+            raise ValueError(f"scene {g} track {i}: boxes are (T_obs, 4 (or 5, closed), 2), got {b.shape}")
+        valid = ~np.isnan(b).all(axis=(1, 2)) if mask is None else np.asarray(mask, dtype=bool)
+        if valid.shape != (b.shape[0],):
+            raise ValueError(f"scene {g} track {i}: the mask has shape {valid.shape} for {b.shape[0]} times")
+        if t_obs is None:
+            t_obs = b.shape[0]
+        elif t_obs != b.shape[0]:
+            raise ValueError(f"scene {g} track {i}: {b.shape[0]} times, the tracks before it {t_obs}")
+        if token in seen:
+            raise ValueError(f"scene {g} track {i}: duplicate token {token!r}")
+        seen.add(token)
+        if token in collided:
+            continue
+        if RED_LIGHT_TOKEN in token:
+            if valid.any():
+                stops.append((token, _ring(b[int(np.argmax(valid))], f"scene {g} token {token!r}")))
+            continue
+        tracks.append((token, np.where(valid[:, None, None], b, 0.0), valid, float(heading), float(speed)))
+    for i, ring in enumerate(rings):
+        stops.append((f"{RED_LIGHT_TOKEN}_{i}", _ring(ring, f"scene {g} stop polygon {i}")))
+    return tracks, stops, t_obs
+
+
+def pack_lead_objects(observations: Sequence, device, stop_polygons: Optional[Sequence] = None,
+                      collided: Optional[Sequence] = None) -> PackedLeadObjects:
+    """What the proposal generator reads of G scenes' observations -> the flat tensors ``dd_proposals`` reads. One
+    entry per scene: the list form ``pack_observations`` takes with a speed per track, ``(token, boxes, heading,
+    is_agent, is_stopped, speed)`` - ``speed`` is ``velocity.magnitude()``, 0 for an object that is no nuPlan Agent -
+    with ``stop_polygons[g]`` the scene's red-light polygons as (n, 2) rings (closing edge implied) and
+    ``collided[g]`` its ``collided_track_ids``; or a duck-typed ``PDMObservation``, read as ``pack_observations`` reads
+    it (map t for time t). Tokens in the collided ids are DROPPED: the generator skips them. Tokens containing
+    "red_light" are KEPT, as stop polygons (their shape at the first time they appear: they are static). Raises
+    ``ValueError`` on what ``pack_observations`` rejects, with 41 in place of 50 times, and on a ring of fewer than 3
+    vertices or with a non-finite vertex."""
+    boxes, valid, heading, speed, off, tokens = [], [], [], [], [0], []
+    verts, ring_off, scene_ring_off = [], [0], [0]
+    t_obs = None
+    for g, entry in enumerate(observations):
+        duck = hasattr(entry, "_occupancy_maps")
+        rings = [] if duck or stop_polygons is None else stop_polygons[g]
+        skip = set() if duck or collided is None else set(collided[g])
+        tracks, stops, t_scene = _scene_lead_objects(entry, g, rings, skip)
+        if t_scene is not None:
+            if t_scene < MIN_LEAD_TIMES:
+                raise ValueError(f"scene {g}: T_obs = {t_scene} is below {MIN_LEAD_TIMES} (the update at 40 reads map 40)")
+            if t_obs is not None and t_obs != t_scene:
+                raise ValueError(f"scene {g}: T_obs = {t_scene}, the scenes before it {t_obs}")
+            t_obs = t_scene
+        names = []
+        for token, b, v, h, sp in tracks:
+            if not np.isfinite(b[v]).all():
+                raise ValueError(f"scene {g} token {token!r}: non-finite box where the object is present")
+            if not np.isfinite(h) or not np.isfinite(sp):
+                raise ValueError(f"scene {g} token {token!r}: non-finite heading or speed")
+            boxes.append(b), valid.append(v), heading.append(h), speed.append(sp), names.append(token)
+        off.append(len(heading))
+        for token, ring in stops:
+            verts.append(ring), names.append(token)
+            ring_off.append(ring_off[-1] + ring.shape[0])
+        scene_ring_off.append(len(ring_off) - 1)
+        tokens.append(tuple(names))
+    t_obs = t_obs if t_obs is not None else MIN_LEAD_TIMES
+    k = len(heading)
+    if k * t_obs * 8 >= 2 ** 31 or ring_off[-1] * 2 >= 2 ** 31:
+        raise ValueError(f"{k} tracks x {t_obs} times or {ring_off[-1]} ring vertices do not fit the int32 offsets")
+    dev = torch.device(device)
+    b = np.stack(boxes) if k else np.zeros((0, t_obs, 4, 2))
+    v = np.stack(valid).astype(np.uint8) if k else np.zeros((0, t_obs), dtype=np.uint8)
+    f64 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(dev)  # noqa: E731
+    i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+    return PackedLeadObjects(f64(b), torch.from_numpy(v).to(dev), f64(heading), f64(speed), i32(off),
+                             f64(np.concatenate(verts) if verts else np.zeros((0, 2))), i32(ring_off),
+                             i32(scene_ring_off), tuple(tokens))
+
+
+def default_idm_params(lib=None) -> _lib.DDIdmParams:
+    """``dd_default_idm_params``: min gap 1 m, headway 1.5 s, acceleration 1.5 and deceleration 3 m/s^2, dt 0.1 s, the
+    exponent 10, the leader update every 2 steps, a corridor of 50 poses (metric_cache_processor.py:44-59)."""
+    p = _lib.DDIdmParams()
+    (lib or _lib.load()).dd_default_idm_params(ctypes.byref(p))
+    return p
+
+
+def _idm_params(params: Union[None, _lib.DDIdmParams, Mapping], lib) -> _lib.DDIdmParams:
+    if isinstance(params, _lib.DDIdmParams):
+        return params
+    p = default_idm_params(lib)
+    for k, v in (params or {}).items():
+        if k not in dict(p._fields_):
+            raise ValueError(f"unknown IDM parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def generate_proposals(paths, lead_objects, ego_states: torch.Tensor, target_velocities, params=None,
+                       details: bool = False, stream: Optional[torch.cuda.Stream] = None, area_params=None,
+                       device=None) -> Proposals:
+    """``PDMGenerator.generate_proposals`` (pdm_generator.py:68-95) on the device. ``paths``: ``pack_paths``' result for
+    the G scenes (or what it takes: packed here); ``lead_objects``: ``pack_lead_objects``' result (or a sequence of
+    duck-typed ``PDMObservation``: packed here); ``ego_states`` (G, 11) float64 start states; ``target_velocities``
+    (G, L): the target velocity of each of the L <= 64 IDM policies per scene (``speed_limit_fraction * speed_limit``,
+    or the fallback) - a host array is checked (positive, finite) and moved; a device tensor is trusted. Returns a
+    ``Proposals``: ``proposals`` (G, P L, 41, 3) float64 in ``PDMProposalManager``'s order (lateral-major), which is
+    what ``simulate_proposals`` takes flattened; with ``details`` also the IDM states, the leader rows and the leader's
+    object index. ``params``: a ``DDIdmParams`` or a mapping of overrides; ``area_params`` gives the vehicle's width
+    and length. The device is ``paths``' if packed, else ``lead_objects``', else ``ego_states``', else ``device``. A
+    bad argument raises ``ValueError`` with ``dd_last_error()``'s text."""
+    lib = _lib.load()
+    dev = None
+    for t in (paths.verts if isinstance(paths, PackedPaths) else None,
+              lead_objects.boxes if isinstance(lead_objects, PackedLeadObjects) else None,
+              ego_states if isinstance(ego_states, torch.Tensor) else None,
+              target_velocities if isinstance(target_velocities, torch.Tensor) else None):
+        if t is not None and t.device.type == "cuda":
+            dev = t.device
+            break
+    if dev is None:
+        dev = torch.device("cuda" if device is None else device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(paths, PackedPaths):
+        paths = pack_paths(paths, dev)
+    if not isinstance(lead_objects, PackedLeadObjects):
+        lead_objects = pack_lead_objects(lead_objects, dev)
+    for name, t, dt in (("paths.verts", paths.verts, torch.float64), ("paths.progress", paths.progress, torch.float64),
+                        ("paths.path_off", paths.path_off, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor on {dev}")
+    _fields_on(PackedLeadObjects(*lead_objects[:8], ()),
+               (torch.float64, torch.uint8, torch.float64, torch.float64, torch.int32, torch.float64, torch.int32,
+                torch.int32), dev, "lead_objects")
+    ego = _ego(ego_states, dev)
+    scenes = int(ego.shape[0])
+    per_scene = int(paths.paths_per_scene)
+    if per_scene < 1 or int(paths.path_off.numel()) != scenes * per_scene + 1:
+        raise ValueError(f"paths holds {int(paths.path_off.numel()) - 1} paths, {per_scene} per scene, for {scenes} "
+                         "scenes (the rows of ego_states)")
+    if int(lead_objects.scene_track_off.numel()) != scenes + 1 or int(lead_objects.scene_ring_off.numel()) != scenes + 1:
+        raise ValueError(f"lead_objects holds {int(lead_objects.scene_track_off.numel()) - 1} scenes for {scenes} (the "
+                         "rows of ego_states)")
+    k = int(lead_objects.heading.numel())
+    b = lead_objects.boxes
+    if b.dim() != 4 or tuple(b.shape[2:]) != (4, 2) or b.shape[0] != k or tuple(lead_objects.valid.shape) != \
+            (k, b.shape[1]) or int(lead_objects.speed.numel()) != k or int(lead_objects.stop_verts.numel()) % 2:
+        raise ValueError("lead_objects is not what pack_lead_objects returns: boxes / valid / speed do not fit heading")
+    rings = int(lead_objects.ring_off.numel()) - 1
+    host = None
+    if isinstance(target_velocities, torch.Tensor) and target_velocities.device.type == "cuda":
+        targets = target_velocities
+    else:
+        host = np.ascontiguousarray(np.asarray(target_velocities, dtype=np.float64))
+        targets = torch.from_numpy(host)
+    if targets.dtype != torch.float64 or targets.dim() != 2 or targets.shape[0] != scenes:
+        raise ValueError(f"target_velocities must be float64 ({scenes}, L), got {tuple(targets.shape)} {targets.dtype}")
+    policies = int(targets.shape[1])
+    targets = targets.to(dev).contiguous()
+    p, ap = _idm_params(params, lib), _area_params(area_params, lib)
+    pp = _lib.DDPaths(paths.verts.data_ptr() or None, paths.progress.data_ptr() or None,
+                      paths.path_off.data_ptr() or None, per_scene, int(paths.progress.numel()))
+    lo = _lib.DDLeadObjects(b.data_ptr() or None, lead_objects.valid.data_ptr() or None,
+                            lead_objects.heading.data_ptr() or None, lead_objects.speed.data_ptr() or None,
+                            lead_objects.scene_track_off.data_ptr() or None, k, int(b.shape[1]),
+                            lead_objects.stop_verts.data_ptr() or None, lead_objects.ring_off.data_ptr() or None,
+                            lead_objects.scene_ring_off.data_ptr() or None, rings)
+    n = scenes * per_scene * policies
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):  # the outputs and the scratch belong to the stream that runs
+        out = torch.empty((scenes, per_scene * policies, NUM_STATES, 3), dtype=torch.float64, device=dev)
+        idm = torch.empty((scenes, per_scene * policies, NUM_STATES, 2), dtype=torch.float64, device=dev) if details else None
+        lead = torch.empty((scenes, per_scene * policies, NUM_STATES, 3), dtype=torch.float64, device=dev) if details else None
+        index = torch.empty((scenes, per_scene * policies, NUM_STATES), dtype=torch.int32, device=dev) if details else None
+        size = lib.dd_proposals_work(scenes, per_scene, k, rings)
+        work = torch.empty((size,), dtype=torch.float64, device=dev)
+        rc = lib.dd_proposals(ctypes.byref(pp), ctypes.byref(lo), ego.data_ptr(), targets.data_ptr() or None,
+                              host.ctypes.data if host is not None and host.size else None, scenes, policies,
+                              ctypes.byref(p), ctypes.byref(ap), work.data_ptr(), size, out.data_ptr() if n else None,
+                              idm.data_ptr() if details and n else None, lead.data_ptr() if details and n else None,
+                              index.data_ptr() if details and n else None, s.cuda_stream)
+    _raise(rc, lib)
+    return Proposals(out, idm, lead, index)
+
+
+def select_best(scores: PDMScores, states: torch.Tensor, stream: Optional[torch.cuda.Stream] = None
+                ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``dd_pdm_select``: per scene np.argmax of ``scores.score`` (G, n) - the first maximum - as int32 (G), that
+    candidate's states (G, 41, 11) and its ``raw_progress * no_collision * drivable_area`` (G)."""
+    lib = _lib.load()
+    states, lead, n = _states_arg(states, 1)
+    dev = states.device
+    if len(lead) != 2:
+        raise ValueError(f"states must be (G, n, {NUM_STATES}, {STATE_SIZE}), got {tuple(states.shape)}")
+    ins = []
+    for name in ("score", "raw_progress", "no_collision", "drivable_area"):
+        t = getattr(scores, name)
+        if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float64 or tuple(t.shape) != lead:
+            raise ValueError(f"scores.{name} must be a float64 {lead} tensor on {dev}")
+        ins.append(t.contiguous())
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        index = torch.empty((lead[0],), dtype=torch.int32, device=dev)
+        best = torch.empty((lead[0], NUM_STATES, STATE_SIZE), dtype=torch.float64, device=dev)
+        reference = torch.empty((lead[0],), dtype=torch.float64, device=dev)
+        rc = lib.dd_pdm_select(*(t.data_ptr() for t in ins), states.data_ptr(), n, lead[1] if lead[0] else 0,
+                               index.data_ptr(), best.data_ptr(), reference.data_ptr(), s.cuda_stream)
+    _raise(rc, lib)
+    return index, best, reference
+
+
+def pdm_closed(paths, lead_objects, ego_states: torch.Tensor, target_velocities, maps, observations, centerlines, *,
+               idm_params=None, sim_params=None, comfort_params=None, area_params=None, score_params=None,
+               stream: Optional[torch.cuda.Stream] = None, device=None) -> PDMClosed:
+    """The PDM-Closed planner's candidate stage on one stream, nothing leaving the device: ``generate_proposals`` ->
+    ``simulate_proposals`` -> ``pdm_score`` (the scene's P L proposals normalised as a group, ``score_proposals``'
+    rule) -> per scene the first maximum (``dd_pdm_select``). ``maps``, ``observations`` and ``centerlines`` are what
+    ``pdm_score`` takes. Returns a ``PDMClosed``: the scores of all proposals, the best index, the best proposal's
+    simulated states, and ``progress_reference`` (G) - the best proposal's ``raw_progress * no_collision *
+    drivable_area``, the value ``pdm_score(progress_reference=)`` needs to score a planner's candidates as pairs with
+    the PDM-Closed trajectory (navsim/evaluate/pdm_score.py)."""
+    made = generate_proposals(paths, lead_objects, ego_states, target_velocities, idm_params, stream=stream,
+                              area_params=area_params, device=device)
+    dev = made.proposals.device
+    s = stream or torch.cuda.current_stream(dev)
+    scenes, per = int(made.proposals.shape[0]), int(made.proposals.shape[1])
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        states = simulate_proposals(made.proposals.view(scenes * per, NUM_STATES, 3), _ego(ego_states, dev), sim_params,
+                                    per_group=per, stream=s).view(scenes, per, NUM_STATES, STATE_SIZE)
+        scores = pdm_score(states, maps, observations, centerlines, comfort_params=comfort_params,
+                           area_params=area_params, score_params=score_params, stream=s)
+        index, best, reference = select_best(scores, states, stream=s)
+    return PDMClosed(scores, index, best, reference, made.proposals, states)

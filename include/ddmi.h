@@ -36,6 +36,10 @@
  *                  pdm_scorer.py:293-349,414-498, pdm_scorer_utils.py:13-65
  *   dd_progress  <- PDMScorer._calculate_progress               pdm_scorer.py:398-412
  *   dd_pdm_aggregate <- PDMScorer._aggregate_scores             pdm_scorer.py:156-183
+ *   dd_proposals <- PDMGenerator.generate_proposals             pdm_planner/proposal/pdm_generator.py:68-95,185-366
+ *                   with BatchIDMPolicy.propagate (proposal/batch_idm_policy.py:102-168) and PDMPath.interpolate /
+ *                   substring (utils/pdm_path.py:67-105)
+ *   dd_pdm_select <- np.argmax(proposal_scores)                 pdm_planner/abstract_pdm_closed_planner.py
  *
  * Threading: a handle is bound to one device and is not re-entrant; concurrent calls on one
  * handle must be serialised by the caller (the reference runs one agent per worker process,
@@ -573,6 +577,109 @@ int dd_pdm_aggregate(const double* no_collision, const double* drivable_area, co
                      const double* raw_progress, const double* ttc, const uint8_t* comfort, int N, int per_group,
                      const dd_score_params* score_params, const double* progress_reference, double* out_score,
                      double* out_progress, void* stream);
+
+/* ---- PDM-Closed's proposal generation (PDMGenerator.generate_proposals, pdm_generator.py:68-95,185-366, with
+ * BatchIDMPolicy.propagate, batch_idm_policy.py:102-168, and PDMPath.interpolate / substring, pdm_path.py:67-105) on
+ * the GPU: the stage in front of dd_simulate_proposals ---- */
+/* The lateral paths of G scenes, the same number per scene, as flat device arrays; path q = scene q / paths_per_scene,
+ * lateral index q % paths_per_scene. TRUSTED, not validated (diffusiondrive_amd.simulate.pack_paths guarantees it):
+ * path_off starts at 0, never decreases and ends at num_verts; every path has at least 2 vertices, all finite, a
+ * progress that starts at 0, never decreases and ends above 1e-5. */
+typedef struct dd_paths {
+  const double* verts;        /* device double (V, 3): x, y, heading UNWRAPPED along the path (np.unwrap) */
+  const double* progress;     /* device double (V): calculate_progress of each path (its cumulative length from 0) */
+  const int32_t* path_off;    /* device int32 (G * paths_per_scene + 1) */
+  int paths_per_scene;        /* P >= 1 */
+  int num_verts;              /* V, the host's copy of path_off[G P] */
+} dd_paths;
+/* What the generator reads of the observation: the tracks of dd_observations (the tokens in collided_track_ids
+ * dropped, the red-light tokens NOT among them) with a speed per track, and the scenes' stop polygons - the red-light
+ * lane connectors, static over time, simple rings of at least 3 vertices whose closing edge is implied - in
+ * dd_drivable_maps' layout without the polygon level. Object index within a scene: the tracks in order, then the
+ * rings. TRUSTED (simulate.pack_lead_objects guarantees it). */
+typedef struct dd_lead_objects {
+  const double* boxes;             /* device double (K, T_obs, 4, 2) */
+  const uint8_t* valid;            /* device uint8 (K, T_obs) */
+  const double* heading;           /* device double (K): unique_objects[token].center.heading */
+  const double* speed;             /* device double (K): velocity.magnitude(); 0 for an object that is no nuPlan Agent */
+  const int32_t* scene_track_off;  /* device int32 (G + 1) */
+  int num_tracks;                  /* K; with K = 0 the first four may be NULL */
+  int num_times;                   /* T_obs >= 41: the update at time index 40 reads occupancy map 40 */
+  const double* stop_verts;        /* device double (Vs, 2) */
+  const int32_t* ring_off;         /* device int32 (R + 1): ring r = vertices ring_off[r] .. ring_off[r + 1] - 1 */
+  const int32_t* scene_ring_off;   /* device int32 (G + 1): scene g = rings scene_ring_off[g] .. [g + 1] - 1 */
+  int num_rings;                   /* R; with R = 0 stop_verts and ring_off may be NULL */
+} dd_lead_objects;
+/* BatchIDMPolicy's parameters as metric_cache_processor.py:44-59 sets them (one value for all policies: the policies
+ * differ by their target velocity alone), the exponent propagate hard-codes, the generator's update rate and the
+ * number of poses of the TRAJECTORY sampling the corridor's length is taken from (50, not the 40 of the proposals).
+ * The vehicle's width and length are dd_area_params' half_width and half_length. */
+typedef struct dd_idm_params {
+  double min_gap_to_lead_agent;   /* 1.0 m */
+  double headway_time;            /* 1.5 s */
+  double accel_max;               /* 1.5 m/s^2 */
+  double decel_max;               /* 3.0 m/s^2 (positive) */
+  double dt;                      /* 0.1 s */
+  int acceleration_exponent;      /* 10 */
+  int leading_agent_update_rate;  /* 2: the leader is searched at time indices that are multiples of it */
+  int corridor_poses;             /* 50 */
+} dd_idm_params;
+void dd_default_idm_params(dd_idm_params* p);
+/* Device scratch of dd_proposals in doubles for G scenes of P paths, K tracks and R rings in all. Never 0. */
+size_t dd_proposals_work(int G, int P, int K, int R);
+/* ego_states: device double (G, 11) in StateIndex order (rear-axle x, y = columns 0, 1 and velocity x = column 3 are
+ * read). targets: device double (G, L): the target velocity of policy l in scene g (speed_limit_fraction * speed limit,
+ * or the fallback, as BatchIDMPolicy.update forms it), TRUSTED on the device; targets_host: NULL, or a host copy of
+ * the same G L values, which is then checked (a device array cannot be without a copy). L <= 64.
+ *   out_proposals: device double (G P L, 41, 3), x, y, heading: lateral-major in PDMProposalManager's order, proposal
+ *     n = scene n / (P L), path (n / L) % P, policy n % L: what dd_simulate_proposals takes with per_group = P L
+ *   out_idm: device double (N, 41, 2) or NULL: progress, velocity
+ *   out_lead: device double (N, 41, 3) or NULL: the leader's progress, velocity, rear length
+ *   out_lead_index: device int32 (N, 41) or NULL: the object index within the scene (tracks, then rings: K_scene +
+ *     ring), -1 for free driving and for time indices 0 and below the first update
+ * The rules (DESIGN.md section 18 has them at length):
+ *   start: progress = project(rear axle) on the path (dd_progress's rule); state 0 = interpolate(progress); the IDM
+ *     state is (progress, velocity x).
+ *   interpolate(d): d clipped to [1e-5, length]; scipy's linear interp1d over the cumulative progress (searchsorted,
+ *     the index clipped to [1, V - 1], slope * (d - x_lo) + y_lo); heading arctan2(sin, cos); a NaN becomes 0.
+ *   corridor, once per (scene, path): the VERTICES whose progress lies in [progress, progress + |max target| *
+ *     corridor_poses * dt] (both clipped to [0, length]; the interpolated ends are not added); with one or none inside,
+ *     shapely's substring as remembered: the two interpolated ends and the vertices strictly between, one point when the
+ *     ends coincide. Buffered by half_width with square caps as the EXACT offset region (this project's rule: GEOS,
+ *     which cannot be asked here, inscribes polygons in the arcs, at most r (1 - cos(pi / 64)) inside them): a rectangle
+ *     per segment of positive length, the first and last lengthened by r; a closed disc at every interior point; one
+ *     point gives a disc. Intersection is closed.
+ *   leader, at time indices t that are multiples of the update rate (other rows copy the row before; rows before the
+ *     first update are zero, as the reference's array): among the objects valid at t that meet the corridor and whose
+ *     centroid (area centroid at t) projects strictly ahead of the proposal's progress at t - 1, the nearest to the ego
+ *     quad at state t - 1 (dd_ego_areas' corners; 0 where they intersect, else the least distance between the
+ *     boundaries, on coordinates relative to the quad's first corner), the first in object order on a tie. Row =
+ *     (progress[t - 1] + distance, speed * cos(normalize(heading - ego heading)) for a track, .). With nothing ahead:
+ *     (path length, ., half_length). The reference fills one scratch row for the proposals of a path in policy order
+ *     and never clears it: a value marked '.' is what an earlier proposal of the same path wrote at the same t, 0 if
+ *     none did (a leader after a free-driving proposal keeps rear length half_length; a ring after a track keeps the
+ *     track's velocity).
+ *   IDM: s* = (min_gap + v headway) + v (v - v_lead) / (2 sqrt(accel decel)); s_a = max((x_lead - x) - l_r, min_gap);
+ *     a = clip(accel ((1 - (v / target)^exponent) - (s* / s_a)^2), -decel, accel); x += dt v; v += dt a.
+ * Three launches on `stream` (setup per path; corridor membership per (path, update time); one wavefront per path
+ * walking its L proposals); no allocation, copy, synchronisation or atomics: two calls are bit-equal. DD_ERR_INVALID
+ * before any device work, naming the argument or field in dd_last_error(): G <= 0, L outside 1..64, a null paths /
+ * objects / ego_states / targets / idm_params / area_params / work / out_proposals, paths_per_scene <= 0, null path
+ * arrays, num_verts < 2 G P, num_tracks or num_rings negative, a null array that a positive count needs, null
+ * scene_track_off / scene_ring_off, num_times < 41, an IDM or vehicle figure that is not positive and finite, an
+ * exponent, update rate or corridor_poses that is not positive, an update rate above 40, a targets_host entry that is
+ * not positive and finite, work_doubles below dd_proposals_work(G, P, K, R). */
+int dd_proposals(const dd_paths* paths, const dd_lead_objects* objects, const double* ego_states,
+                 const double* targets, const double* targets_host, int G, int L, const dd_idm_params* idm_params,
+                 const dd_area_params* area_params, double* work, size_t work_doubles, double* out_proposals,
+                 double* out_idm, double* out_lead, int32_t* out_lead_index, void* stream);
+/* The pick of PDM-Closed: per scene np.argmax of its per_group scores (the first maximum; a NaN counts as the
+ * maximum), that candidate's states (N, 41, 11) -> out_states (G, 41, 11) and its raw_progress * (no_collision *
+ * drivable_area) -> out_reference (G): the progress_reference dd_pdm_aggregate takes. One launch, one wavefront per
+ * scene. DD_ERR_INVALID: N <= 0, per_group <= 0, N % per_group != 0, a null argument. */
+int dd_pdm_select(const double* score, const double* raw_progress, const double* no_collision,
+                  const double* drivable_area, const double* states, int N, int per_group, int32_t* out_index,
+                  double* out_states, double* out_reference, void* stream);
 
 /* ---- input feature builder (TransfuserFeatureBuilder.compute_features on the GPU) ---------- */
 /* Camera feature (transfuser_features.py:57-77): crop + stitch + cv2 INTER_LINEAR resize +
