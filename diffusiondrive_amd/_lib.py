@@ -317,6 +317,21 @@ _SIGS = {
     "dd_op_bilinear_view": (ctypes.c_int, [ctypes.POINTER(DDOpView), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, ctypes.POINTER(DDOpView), ctypes.c_int, ctypes.c_int,
                                            ctypes.c_int, c_void_p]),
+    "dd_op_mha_small_view": (ctypes.c_int, [c_void_p, ctypes.c_int64, ctypes.c_int64, c_void_p, c_void_p,
+                                            ctypes.c_int64, ctypes.c_int64, c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, c_void_p]),
+    "dd_op_bev_sample_attn_s": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_float, ctypes.c_float, c_void_p]),
+    "dd_op_bev_taps": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                      ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
+                                      c_void_p]),
+    "dd_op_bev_sample_attn_gathered": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                      ctypes.c_int, ctypes.c_float, ctypes.c_float, c_void_p]),
+    "dd_op_avgpool_view": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDOpView), c_void_p, c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

@@ -517,4 +517,68 @@ int dd_op_bilinear_view(const dd_op_view* in, int B, int Hi, int Wi, int C, cons
   });
 }
 
+int dd_op_mha_small_view(const float* q, int64_t ldq, int64_t q_bstride, const float* k, const float* v, int64_t ldkv,
+                         int64_t kv_bstride, float* out, int64_t ldo, int64_t o_bstride, int B, int Lq, int Lk, int nh,
+                         int hd, int kv_div, void* stream) {
+  return op_guard([&] {
+    if (!q || !k || !v || !out) throw std::invalid_argument("dd_op_mha_small_view: null q, k, v or out");
+    if (B < 1 || Lq < 1 || Lk < 1 || nh < 1 || hd < 1 || kv_div < 1)
+      throw std::invalid_argument("dd_op_mha_small_view: B, Lq, Lk, nh, hd and kv_div must be positive");
+    const int64_t d = (int64_t)nh * hd;
+    if (ldq < d || ldkv < d || ldo < d)
+      throw std::invalid_argument("dd_op_mha_small_view: a leading dimension below nh * hd");
+    launch_mha_small(q, ldq, k, v, ldkv, out, ldo, B, Lq, Lk, nh, hd, q_bstride, kv_bstride, o_bstride, S(stream),
+                     kv_div);
+  });
+}
+
+int dd_op_bev_sample_attn_s(const float* logits, const float* pts, const float* value, float* out, int B, int Q, int P,
+                            int Hv, int Wv, int C, int samples, float inv_max_x, float inv_max_y, void* stream) {
+  return op_guard([&] {
+    if (!logits || !pts || !value || !out)
+      throw std::invalid_argument("dd_op_bev_sample_attn_s: null logits, pts, value or out");
+    if (B < 1 || Q < 1 || P < 1 || Hv < 1 || Wv < 1 || C < 1 || samples < 1)
+      throw std::invalid_argument("dd_op_bev_sample_attn_s: B, Q, P, Hv, Wv, C and samples must be positive");
+    launch_bev_sample_attn(logits, pts, value, out, B, Q, P, Hv, Wv, C, inv_max_x, inv_max_y, S(stream), samples);
+  });
+}
+
+int dd_op_bev_taps(const float* pts, int* rows, int* slots, int B, int Q, int P, int Hv, int Wv, float inv_max_x,
+                   float inv_max_y, int samples, void* stream) {
+  bool launched = true;
+  const int rc = op_guard([&] {
+    if (!pts || !rows) throw std::invalid_argument("dd_op_bev_taps: null pts or rows");
+    if (B < 1 || Q < 1 || P < 1 || Hv < 1 || Wv < 1 || samples < 1)
+      throw std::invalid_argument("dd_op_bev_taps: B, Q, P, Hv, Wv and samples must be positive");
+    if (slots)
+      launched = launch_bev_tap_dedup(pts, rows, slots, B, Q, P, Hv, Wv, inv_max_x, inv_max_y, S(stream), samples);
+    else
+      launch_bev_tap_rows(pts, rows, B, Q, P, Hv, Wv, inv_max_x, inv_max_y, S(stream), samples);
+  });
+  return rc != DD_OK ? rc : launched ? 1 : 0;
+}
+
+int dd_op_bev_sample_attn_gathered(const float* logits, const float* pts, const float* vrows, const int* slots,
+                                   float* out, int B, int Q, int P, int Hv, int Wv, int C, float inv_max_x,
+                                   float inv_max_y, void* stream) {
+  return op_guard([&] {
+    if (!logits || !pts || !vrows || !out)
+      throw std::invalid_argument("dd_op_bev_sample_attn_gathered: null logits, pts, vrows or out");
+    if (B < 1 || Q < 1 || P < 1 || Hv < 1 || Wv < 1 || C < 1)
+      throw std::invalid_argument("dd_op_bev_sample_attn_gathered: B, Q, P, Hv, Wv and C must be positive");
+    launch_bev_sample_attn_gathered(logits, pts, vrows, slots, out, B, Q, P, Hv, Wv, C, inv_max_x, inv_max_y,
+                                    S(stream));
+  });
+}
+
+int dd_op_avgpool_view(const float* in, int B, int H, int W, int C, int oh, int ow, const dd_op_view* out,
+                       const float* add, void* stream) {
+  return op_guard([&] {
+    if (!in || !out || !out->p) throw std::invalid_argument("dd_op_avgpool_view: null in or out view");
+    if (B < 1 || H < 1 || W < 1 || C < 1 || oh < 1 || ow < 1)
+      throw std::invalid_argument("dd_op_avgpool_view: B, H, W, C, oh and ow must be positive");
+    launch_avgpool(in, B, H, W, C, oh, ow, view_of(*out), add, S(stream));
+  });
+}
+
 }  // extern "C"

@@ -841,6 +841,29 @@ int dd_op_layernorm_ld(const float* x, int64_t ldx, const float* res, int64_t ld
 /* dd_op_bilinear / dd_op_bilinear_add (accumulate = 1) on strided views. */
 int dd_op_bilinear_view(const dd_op_view* in, int B, int Hi, int Wi, int C, const dd_op_view* out, int Ho, int Wo,
                         int accumulate, void* stream);
+/* dd_op_mha_small with the launcher's own operand form: row i of scene b of q / out at b q_bstride + i ldq
+ * (b o_bstride + i ldo), key / value row j of K / V batch b / kv_div at (b / kv_div) kv_bstride + j ldkv (k and v may
+ * point into one interleaved buffer); kv_div consecutive scenes share one K / V batch (B % kv_div == 0). */
+int dd_op_mha_small_view(const float* q, int64_t ldq, int64_t q_bstride, const float* k, const float* v, int64_t ldkv,
+                         int64_t kv_bstride, float* out, int64_t ldo, int64_t o_bstride, int B, int Lq, int Lk, int nh,
+                         int hd, int kv_div, void* stream);
+/* dd_op_bev_sample_attn with `samples` consecutive scenes reading one value map (value holds B / samples maps) and the
+ * two point scales: grid x = pts[..., 1] inv_max_x, grid y = pts[..., 0] inv_max_y. */
+int dd_op_bev_sample_attn_s(const float* logits, const float* pts, const float* value, float* out, int B, int Q, int P,
+                            int Hv, int Wv, int C, int samples, float inv_max_x, float inv_max_y, void* stream);
+/* The tap tables of the gathered value_proj. slots null: rows[(ip) 4 + t] = the map pixel (image b / samples) tap t
+ * of point ip reads, -1 where zero padding applies. slots given: the deduplicated form - rows[b Q P 4 + j] the j-th
+ * distinct tap pixel of scene b in pixel order (-1 past its count), slots[ip 4 + t] the index into rows of the tap's
+ * pixel (-1: padded). Returns 1 if launched, 0 if the dedup form refuses the shape (nothing written), < 0 on error. */
+int dd_op_bev_taps(const float* pts, int* rows, int* slots, int B, int Q, int P, int Hv, int Wv, float inv_max_x,
+                   float inv_max_y, int samples, void* stream);
+/* The sampling on gathered rows: tap t of point ip reads vrows[slots[ip 4 + t]] (slots null: vrows[ip 4 + t]). */
+int dd_op_bev_sample_attn_gathered(const float* logits, const float* pts, const float* vrows, const int* slots,
+                                   float* out, int B, int Q, int P, int Hv, int Wv, int C, float inv_max_x,
+                                   float inv_max_y, void* stream);
+/* dd_op_avgpool into a strided (n, oh, ow, c) view, plus add[(y ow + x) C + c] (nullable; one table for every n). */
+int dd_op_avgpool_view(const float* in, int B, int H, int W, int C, int oh, int ow, const dd_op_view* out,
+                       const float* add, void* stream);
 
 #ifdef __cplusplus
 }

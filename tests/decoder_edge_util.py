@@ -100,41 +100,58 @@ def record_oracle_activations(rec):
         om.layer_norm, om.linear, om.conv = orig
 
 
-def check_gathered_taps(pts, rows, slots, counts, vals, dense, B, tol, Q=20, P=8, HB=64):
-    """The gathered value_proj's dedup of one (step, layer) against the points it was made from.
-
-    ``pts`` (B*Q*P, 2) the layer's trajectory points (the device's own), ``rows`` / ``slots`` (B*Q*P*4,) and ``counts``
-    (B,) the int32 dedup tables, ``vals`` (B*Q*P*4, 256) the gathered rows, ``dense`` (B*HB*HB, 256) the fp32 dense
-    value map of the layer. The tap geometry follows F.grid_sample's align_corners=False / zero padding in float32
-    arithmetic (every operation on the point is exact or a single rounding, so the floor is the kernel's); each
-    scene's row list is exactly its distinct in-map tap pixels in pixel order, -1 past the count; the counts match;
-    every tap's slot is -1 exactly where the tap is zero-padded and points to its pixel otherwise; every live gathered
-    row equals the dense map at its pixel within ``tol`` (relative to max(1, max |map row|)).
-    Returns (padded taps, live taps, max relative row error)."""
-    cap = Q * P * 4
+def tap_pixels(pts, B, Q=20, P=8, HB=64, WB=None, samples=1, inv_max_x=1.0 / 32.0, inv_max_y=1.0 / 32.0):
+    """The map pixel every bilinear tap of every point reads, (B*Q*P*4,) int64 in the order nw, ne, sw, se, -1 where
+    zero padding applies: bev_tap_geometry (decoder.hip) restated in float32 numpy in the kernel's operation order -
+    grid x = pts[:, 1] * inv_max_x over the map's width WB, grid y = pts[:, 0] * inv_max_y over its height HB, every
+    operation a single rounding, so the floor is the kernel's. Scene b reads map image b // samples. Also returns
+    (ix, iy) as float32."""
+    WB = HB if WB is None else WB
+    one, two = np.float32(1), np.float32(2)
     p32 = np.asarray(pts).astype(np.float32).reshape(B * Q * P, 2)
-    ix = ((p32[:, 1] / np.float32(32) + 1) * np.float32(HB) - 1) / 2
-    iy = ((p32[:, 0] / np.float32(32) + 1) * np.float32(HB) - 1) / 2
+    ix = ((p32[:, 1] * np.float32(inv_max_x) + one) * np.float32(WB) - one) / two
+    iy = ((p32[:, 0] * np.float32(inv_max_y) + one) * np.float32(HB) - one) / two
+    assert ix.dtype == np.float32 and iy.dtype == np.float32
     x0, y0 = np.floor(ix).astype(np.int64), np.floor(iy).astype(np.int64)
-    b = np.arange(B * Q * P) // (Q * P)
+    img = np.arange(B * Q * P) // (Q * P) // samples
     pix = []
     for dy, dx in ((0, 0), (0, 1), (1, 0), (1, 1)):
         yy, xx = y0 + dy, x0 + dx
-        ok = (yy >= 0) & (yy < HB) & (xx >= 0) & (xx < HB)
-        pix.append(np.where(ok, (b * HB + yy) * HB + xx, -1))
-    pix = np.stack(pix, 1).reshape(-1)
+        ok = (yy >= 0) & (yy < HB) & (xx >= 0) & (xx < WB)
+        pix.append(np.where(ok, (img * HB + yy) * WB + xx, -1))
+    return np.stack(pix, 1).reshape(-1), ix, iy
+
+
+def check_gathered_taps(pts, rows, slots, counts, vals, dense, B, tol, Q=20, P=8, HB=64, WB=None, samples=1,
+                        inv_max_x=1.0 / 32.0, inv_max_y=1.0 / 32.0):
+    """The gathered value_proj's dedup of one (step, layer) against the points it was made from.
+
+    ``pts`` (B*Q*P, 2) the layer's trajectory points (the device's own), ``rows`` / ``slots`` (B*Q*P*4,) and ``counts``
+    (B,) the int32 dedup tables (``counts`` None: not checked), ``vals`` (B*Q*P*4, C) the gathered rows (None: not
+    checked), ``dense`` (B/samples*HB*WB, C) the fp32 dense value map of the layer. The tap geometry (tap_pixels)
+    follows F.grid_sample's align_corners=False / zero padding in float32 arithmetic; ``samples`` consecutive scenes
+    read one map image (pixel index from b // samples) while each scene's row list stays at its own base b * Q*P*4.
+    Each scene's row list is exactly its distinct in-map tap pixels in pixel order, -1 past the count; the counts
+    match; every tap's slot is -1 exactly where the tap is zero-padded and points to its pixel otherwise, inside its
+    own scene's block; every live gathered row equals the dense map at its pixel within ``tol`` (relative to
+    max(1, max |map row|)).
+    Returns (padded taps, live taps, max relative row error)."""
+    cap = Q * P * 4
+    pix, _, _ = tap_pixels(pts, B, Q, P, HB, WB, samples, inv_max_x, inv_max_y)
     for s_ in range(B):
         tp = pix[s_ * cap:(s_ + 1) * cap]
         uniq = np.unique(tp[tp >= 0])
         rs = rows[s_ * cap:(s_ + 1) * cap]
         assert np.array_equal(rs[:len(uniq)], uniq) and (rs[len(uniq):] == -1).all(), s_
-        assert counts[s_] == len(uniq), (s_, counts[s_], len(uniq))  # the compacted launch's row counts
+        if counts is not None:
+            assert counts[s_] == len(uniq), (s_, counts[s_], len(uniq))  # the compacted launch's row counts
     assert np.array_equal(slots < 0, pix < 0)
     live = slots >= 0
+    assert np.array_equal(slots[live] // cap, np.flatnonzero(live) // cap), "a slot outside its scene's row block"
     assert np.array_equal(rows[slots[live]], pix[live])
     used = rows >= 0
     err = 0.0
-    if used.any():
+    if vals is not None and used.any():
         ref = dense[rows[used]]
         err = float(np.abs(vals[used] - ref).max() / max(1.0, np.abs(ref).max()))
     assert err <= tol, err

@@ -495,9 +495,9 @@ def test_bev_sample_attn(gpu):
     pts[0, 0, 0] = torch.tensor([40.0, -50.0])  # outside the BEV: zero padding
     pts[0, 0, 1] = torch.tensor([31.7, 31.9])   # partially outside
     value = rnd(B, C, H, W, seed=23)
-    grid = torch.stack([pts[..., 1] / 32.0, pts[..., 0] / 32.0], -1)
-    s = F.grid_sample(value, grid, mode="bilinear", padding_mode="zeros", align_corners=False)
-    ref = (torch.softmax(logits, -1).unsqueeze(1) * s).sum(-1).permute(0, 2, 1)
+    grid = torch.stack([pts[..., 1].double() / 32.0, pts[..., 0].double() / 32.0], -1)  # the reference in float64
+    s = F.grid_sample(value.double(), grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+    ref = (torch.softmax(logits.double(), -1).unsqueeze(1) * s).sum(-1).permute(0, 2, 1)
     out = nans(B, Q, C, device=DEV)
     ld, pd, vd = g(logits), g(pts), g(value.permute(0, 2, 3, 1))
     ok(gpu.dd_op_bev_sample_attn(ld.data_ptr(), pd.data_ptr(), vd.data_ptr(), out.data_ptr(), B, Q, P, H, W, C,
