@@ -332,6 +332,11 @@ _SIGS = {
                                                       ctypes.c_int, ctypes.c_float, ctypes.c_float, c_void_p]),
     "dd_op_avgpool_view": (ctypes.c_int, [c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.POINTER(DDOpView), c_void_p, c_void_p]),
+    "dd_op_vproj_limits": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "dd_op_vproj": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int,
+                                   ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                   ctypes.c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
 }
 
 EXPORTED = tuple(_SIGS)

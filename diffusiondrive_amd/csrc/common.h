@@ -470,7 +470,12 @@ struct VprojArgs {
 };
 bool vproj_supported(int C, int Cout, int H, int W);
 size_t vproj_tiles(int B, int cap);
-void launch_vproj(const VprojArgs& a, hipStream_t st);
+// stages (union form only): bit 0 = the union-staged launch, bit 1 = the gathered launch for the tiles it flagged.
+// The forward runs both in one call; dd_op_vproj runs them one by one and reads the fallback flags in between.
+constexpr int kVprojUnion = 1, kVprojFallback = 2;
+void launch_vproj(const VprojArgs& a, hipStream_t st, int stages = kVprojUnion | kVprojFallback);
+// the union-staged kernel's capacity: union rows one buffer stages, keys its bitmap spans
+void vproj_limits(int* umax_rows, int* range_keys);
 
 // ----------------------------------------------------------------------------------------
 // Bandwidth / small kernels (elementwise.hip)

@@ -1,8 +1,13 @@
-// Single-kernel C-ABI entry points (include/ddmi.h, "single-op entry points"): used by the GPU
-// parity tests to check each kernel in isolation against PyTorch-CPU fp32 on the same inputs.
+// Single-kernel C-ABI entry points (include/ddmi.h, "single-op entry points"): used by the GPU parity tests to check
+// each kernel in isolation against a float64 restatement of the operation on the same inputs - a max-norm bar per
+// tensor (test_ops_gpu.py, test_op_views_gpu.py, test_attn_views_gpu.py) and, for the f16x3 kernels, a per-element
+// bound with a measured factor (test_f16x3_bound_gpu.py, test_vproj_tables_gpu.py) - with the operands inside
+// poisoned guards where the entry takes views or row tables.
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
+#include <utility>
 
 #include "../../include/ddmi.h"
 #include "common.h"
@@ -568,6 +573,143 @@ int dd_op_bev_sample_attn_gathered(const float* logits, const float* pts, const 
       throw std::invalid_argument("dd_op_bev_sample_attn_gathered: B, Q, P, Hv, Wv and C must be positive");
     launch_bev_sample_attn_gathered(logits, pts, vrows, slots, out, B, Q, P, Hv, Wv, C, inv_max_x, inv_max_y,
                                     S(stream));
+  });
+}
+
+int dd_op_vproj_limits(int* umax_rows, int* range_keys) {
+  return op_guard([&] {
+    if (!umax_rows || !range_keys) throw std::invalid_argument("dd_op_vproj_limits: null umax_rows or range_keys");
+    vproj_limits(umax_rows, range_keys);
+  });
+}
+
+namespace {
+struct DevWords {  // a device scratch array, freed on every way out
+  void* p = nullptr;
+  void alloc(size_t bytes) { DD_HIP_CHECK(hipMalloc(&p, std::max<size_t>(bytes, 16))); }
+  ~DevWords() {
+    if (p) (void)hipFree(p);
+  }
+};
+// a caller's row table, read back: counts within [0, cap] and every listed key a pixel of the map, so that neither
+// kernel is launched on a table that would take it outside its operands
+void vproj_check_table(const int* rows, const int* counts, int B, int cap, int nimg, const char* which) {
+  std::vector<int> hc((size_t)B), hr((size_t)B * cap);
+  DD_HIP_CHECK(hipMemcpy(hc.data(), counts, hc.size() * sizeof(int), hipMemcpyDeviceToHost));
+  DD_HIP_CHECK(hipMemcpy(hr.data(), rows, hr.size() * sizeof(int), hipMemcpyDeviceToHost));
+  for (int b = 0; b < B; ++b) {
+    if (hc[b] < 0 || hc[b] > cap)
+      throw std::invalid_argument(std::string("dd_op_vproj: ") + which + " counts outside [0, cap]");
+    for (int l = 0; l < hc[b]; ++l) {
+      const int k = hr[(size_t)b * cap + l];
+      if (k < 0 || k >= nimg * 4096)
+        throw std::invalid_argument(std::string("dd_op_vproj: ") + which + " rows name a pixel outside the map");
+    }
+  }
+}
+}  // namespace
+
+int dd_op_vproj(const float* map, const float* wgt, const float* bias, const int* rows, const int* counts, float* out,
+                int B, int cap, int nimg, int union_stage, int usplit, int umax, int ldh_pad, unsigned part_fill,
+                unsigned* flags, const int* rows2, const int* counts2, float* out2, unsigned* fb_seen,
+                unsigned* fb_after, unsigned* ucnt_after, void* stream) {
+  return op_guard([&] {
+    const std::pair<const void*, const char*> must[] = {{map, "map"},   {wgt, "wgt"},       {bias, "bias"},
+                                                        {rows, "rows"}, {counts, "counts"}, {out, "out"}};
+    for (const auto& m : must)
+      if (!m.first) throw std::invalid_argument(std::string("dd_op_vproj: null ") + m.second);
+    if (B < 1 || cap < 1 || (int64_t)B * cap > (1 << 22))
+      throw std::invalid_argument("dd_op_vproj: B and cap must be positive, B * cap at most 2^22 rows");
+    if (nimg < 0 || nimg > (1 << 16)) throw std::invalid_argument("dd_op_vproj: nimg must be 0 (B) .. 65536");
+    if (union_stage != 0 && union_stage != 1) throw std::invalid_argument("dd_op_vproj: union_stage must be 0 or 1");
+    if (ldh_pad < 0 || ldh_pad % 8 || ldh_pad > 1024)
+      throw std::invalid_argument("dd_op_vproj: ldh_pad must be a multiple of 8 in 0 .. 1024");
+    if ((rows2 != nullptr) != (counts2 != nullptr) || (rows2 != nullptr) != (out2 != nullptr))
+      throw std::invalid_argument("dd_op_vproj: rows2, counts2 and out2 go together");
+    constexpr int kCout = 256, kK = 9 * 256;
+    const hipStream_t st = S(stream);
+    DD_HIP_CHECK(hipStreamSynchronize(st));
+    // split the (device) fp32 weights on the host exactly as dd_create does (weights.cpp:prep_split)
+    std::vector<float> hw((size_t)kCout * kK);
+    DD_HIP_CHECK(hipMemcpy(hw.data(), wgt, hw.size() * sizeof(float), hipMemcpyDeviceToHost));
+    Arena ar;
+    const SplitW x = prep_split(ar, hw.data(), kCout, kK);
+    size_t hi = x.hi, lo = x.lo;
+    const int ldh = x.ldh + ldh_pad;
+    if (ldh_pad) {
+      // the same images with longer rows; the padding holds fp16 NaNs, which neither kernel may read
+      auto widen = [&](size_t off) {
+        std::vector<uint16_t> img((size_t)kCout * ldh, (uint16_t)0x7e00);
+        const uint16_t* src = reinterpret_cast<const uint16_t*>(ar.host(off));
+        for (int r = 0; r < kCout; ++r)
+          std::memcpy(&img[(size_t)r * ldh], src + (size_t)r * x.ldh, (size_t)x.ldh * sizeof(uint16_t));
+        return ar.add(reinterpret_cast<const float*>(img.data()), img.size() / 2);
+      };
+      hi = widen(x.hi);
+      lo = widen(x.lo);
+    }
+    ar.upload();
+    const int nreal = nimg > 0 ? nimg : B;
+    if (B <= 256 && nreal <= B) {  // (launch_vproj refuses the others before it launches anything)
+      vproj_check_table(rows, counts, B, cap, nreal, "the first table's");
+      if (rows2) vproj_check_table(rows2, counts2, B, cap, nreal, "the second table's");
+    }
+    // scratch as the forward holds it: zeroed fallback flags and arrival counters, partials of any content
+    const size_t tiles = vproj_tiles(B, cap), words = 2 * ((tiles + 7) / 8 * 8);
+    DevWords fb, ucnt, part;
+    fb.alloc(words * sizeof(unsigned));
+    ucnt.alloc(words * sizeof(unsigned));
+    DD_HIP_CHECK(hipMemsetAsync(fb.p, 0, words * sizeof(unsigned), st));
+    DD_HIP_CHECK(hipMemsetAsync(ucnt.p, 0, words * sizeof(unsigned), st));
+    if (union_stage && usplit > 1 && usplit <= 64) {
+      const size_t n = (size_t)usplit * B * cap * kCout;
+      part.alloc(n * sizeof(float));
+      DD_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(part.p), (int)part_fill, n, st));
+    }
+    VprojArgs v;
+    v.map = map;
+    v.wh = reinterpret_cast<const uint16_t*>(ar.ptr(hi));
+    v.wl = reinterpret_cast<const uint16_t*>(ar.ptr(lo));
+    v.wsinv = ar.ptr(x.sinv);
+    v.ldh = ldh;
+    v.bias = bias;
+    v.rows = rows;
+    v.counts = counts;
+    v.B = B;
+    v.cap = cap;
+    v.nimg = nimg;
+    v.out = out;
+    v.flags = flags;
+    v.union_stage = union_stage;
+    v.umax = umax;
+    v.usplit = usplit;
+    v.fb = static_cast<unsigned*>(fb.p);
+    v.ucnt = static_cast<unsigned*>(ucnt.p);
+    v.part = static_cast<float*>(part.p);
+    if (fb_seen) std::memset(fb_seen, 0, 2 * tiles * sizeof(unsigned));
+    try {  // (the split images die with `ar`, the scratch with this scope: the stream is drained on every way out)
+      if (union_stage) {
+        // the union launch, the flags it raised, then the gathered launch that computes those tiles and clears them
+        launch_vproj(v, st, kVprojUnion);
+        DD_HIP_CHECK(hipStreamSynchronize(st));
+        if (fb_seen) DD_HIP_CHECK(hipMemcpy(fb_seen, fb.p, 2 * tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
+        launch_vproj(v, st, kVprojFallback);
+      } else {
+        launch_vproj(v, st);
+      }
+      if (rows2) {  // the second table on the scratch the first launch left, as one forward's layers follow each other
+        v.rows = rows2;
+        v.counts = counts2;
+        v.out = out2;
+        launch_vproj(v, st);
+      }
+    } catch (...) {
+      (void)hipStreamSynchronize(st);
+      throw;
+    }
+    DD_HIP_CHECK(hipStreamSynchronize(st));
+    if (fb_after) DD_HIP_CHECK(hipMemcpy(fb_after, fb.p, 2 * tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
+    if (ucnt_after) DD_HIP_CHECK(hipMemcpy(ucnt_after, ucnt.p, 2 * tiles * sizeof(unsigned), hipMemcpyDeviceToHost));
   });
 }
 

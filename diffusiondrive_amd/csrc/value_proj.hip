@@ -940,7 +940,12 @@ bool vproj_supported(int C, int Cout, int H, int W) { return C == kC && Cout == 
 
 size_t vproj_tiles(int B, int cap) { return ((size_t)B * cap + VP_BM - 1) / VP_BM; }
 
-void launch_vproj(const VprojArgs& a, hipStream_t st) {
+void vproj_limits(int* umax_rows, int* range_keys) {
+  if (umax_rows) *umax_rows = VU_UMAX;
+  if (range_keys) *range_keys = VU_RBITS;
+}
+
+void launch_vproj(const VprojArgs& a, hipStream_t st, int stages) {
   if (!a.map || !a.wh || !a.wl || !a.wsinv || !a.bias || !a.rows || !a.counts || !a.out)
     throw std::runtime_error("vproj: missing operand");
   if (a.B < 1 || a.B > 256 || a.cap < 1 || a.ldh < 9 * kC || a.ldh % 8)
@@ -964,11 +969,15 @@ void launch_vproj(const VprojArgs& a, hipStream_t st) {
         a.usplit > 8)
       throw std::runtime_error("vproj: the union-staged form needs fallback flags, a power-of-two split <= 8 "
                                "and, split, its counters and partials");
-    hipLaunchKernelGGL(vproj_union_kernel<true>, dim3((unsigned)(t8 * 2 * a.usplit)), dim3(VU_NT), 0, st, a);
-    DD_HIP_CHECK(hipGetLastError());
-    VprojArgs f = a;
-    f.fb_only = 1;  // tiles whose union did not fit: the gathered form, in the union form's arithmetic
-    hipLaunchKernelGGL((vproj_kernel<2, true>), dim3((unsigned)(t8 * 2)), dim3(VP_NT), 0, st, f);
+    if (stages & kVprojUnion) {
+      hipLaunchKernelGGL(vproj_union_kernel<true>, dim3((unsigned)(t8 * 2 * a.usplit)), dim3(VU_NT), 0, st, a);
+      DD_HIP_CHECK(hipGetLastError());
+    }
+    if (stages & kVprojFallback) {
+      VprojArgs f = a;
+      f.fb_only = 1;  // tiles whose union did not fit: the gathered form, in the union form's arithmetic
+      hipLaunchKernelGGL((vproj_kernel<2, true>), dim3((unsigned)(t8 * 2)), dim3(VP_NT), 0, st, f);
+    }
   } else {
     hipLaunchKernelGGL(vproj_kernel<2>, dim3((unsigned)(t8 * 2)), dim3(VP_NT), 0, st, a);
   }

@@ -861,6 +861,30 @@ int dd_op_bev_taps(const float* pts, int* rows, int* slots, int B, int Q, int P,
 int dd_op_bev_sample_attn_gathered(const float* logits, const float* pts, const float* vrows, const int* slots,
                                    float* out, int B, int Q, int P, int Hv, int Wv, int C, float inv_max_x,
                                    float inv_max_y, void* stream);
+/* The capacity of value_proj's union-staged kernel: *umax_rows = the union rows one staging buffer holds, *range_keys
+ * = the keys its bitmap spans. A 256-row tile whose union of 3 x 3 neighbourhoods exceeds the first, or whose
+ * max key - min key + 131 exceeds the second, is computed by the gathered kernel instead. Host only. */
+int dd_op_vproj_limits(int* umax_rows, int* range_keys);
+/* The gathered value_proj (value_proj.hip, launch_vproj) on a caller's row table: out[b cap + l][256] =
+ * ReLU(conv3x3(map) + bias) at pixel rows[b cap + l], l < counts[b]; rows past a group's count are not written.
+ * map: nimg images (64, 64, 256) NHWC (nimg 0 = B); wgt: device fp32 (256, 3, 3, 256), K order (kh, kw, ci), split on
+ * the host as dd_create does, its image rows lengthened by ldh_pad halfs (a multiple of 8; the padding holds NaNs);
+ * rows: B * cap keys image * 4096 + pixel, distinct and ascending within a group, -1 past its count; counts: B.
+ * union_stage 1: the union-staged kernel with K split usplit (1, 2, 4, 8), then the gathered kernel for the tiles
+ * whose key range or union (above min(capacity, umax)) did not fit; 0: the gathered kernel for every tile.
+ * The entry owns the scratch, as the forward holds it: fallback flags and arrival counters [tiles][2] zeroed
+ * (tiles = ceil(B cap / 256)), split partials filled with the word part_fill. It runs the union launch, copies the
+ * flags to fb_seen (host, [tiles][2], nullable: which (tile, half) pairs fell back), runs the fallback launch, then -
+ * rows2 / counts2 / out2 given (all or none) - the whole form again on that second table with the same scratch, and
+ * copies flags and counters to fb_after / ucnt_after (host, [tiles][2], nullable: all zero after a sound launch).
+ * flags (device word, nullable) receives DD_NUM_* bits. Synchronous. DD_ERR_INVALID before any device work, with the
+ * argument named in dd_op_last_error(): a null operand, B or cap < 1, a bad ldh_pad or union_stage; and after the
+ * tables are read back: a count outside [0, cap] or a key outside the map. launch_vproj's own refusals (B > 256,
+ * usplit, nimg > B, an operand not 16-byte aligned) return DD_ERR_RUNTIME before anything is launched. */
+int dd_op_vproj(const float* map, const float* wgt, const float* bias, const int* rows, const int* counts, float* out,
+                int B, int cap, int nimg, int union_stage, int usplit, int umax, int ldh_pad, unsigned part_fill,
+                unsigned* flags, const int* rows2, const int* counts2, float* out2, unsigned* fb_seen,
+                unsigned* fb_after, unsigned* ucnt_after, void* stream);
 /* dd_op_avgpool into a strided (n, oh, ow, c) view, plus add[(y ow + x) C + c] (nullable; one table for every n). */
 int dd_op_avgpool_view(const float* in, int B, int H, int W, int C, int oh, int ow, const dd_op_view* out,
                        const float* add, void* stream);
