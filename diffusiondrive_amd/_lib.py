@@ -150,6 +150,21 @@ class DDIdmParams(ctypes.Structure):
     ]
 
 
+class DDDetections(ctypes.Structure):
+    """dd_detections: the raw detections of G scenes as flat device arrays (include/ddmi.h)."""
+    _fields_ = [("boxes", c_void_p), ("type", c_void_p), ("scene_det_off", c_void_p), ("collided_in", c_void_p),
+                ("num_dets", ctypes.c_int)]
+
+
+class DDObserveParams(ctypes.Structure):
+    """dd_observe_params: the radius, sampling and caps of dd_observe (include/ddmi.h)."""
+    _fields_ = [
+        ("map_radius", ctypes.c_double), ("dt", ctypes.c_double), ("num_samples", ctypes.c_int),
+        ("sample_res", ctypes.c_int), ("max_vehicles", ctypes.c_int), ("max_pedestrians", ctypes.c_int),
+        ("max_bicycles", ctypes.c_int), ("max_static", ctypes.c_int), ("stopped_speed", ctypes.c_double),
+    ]
+
+
 class DDOpView(ctypes.Structure):
     """dd_op_view: a strided (n, h, w, c) operand of the view-taking single-op entries (include/ddmi.h)."""
     _fields_ = [("p", c_void_p), ("sn", ctypes.c_int64), ("sh", ctypes.c_int64), ("sw", ctypes.c_int64),
@@ -243,6 +258,13 @@ _SIGS = {
                                     c_void_p, c_void_p, c_void_p]),
     "dd_pdm_select": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dd_default_observe_params": (None, [ctypes.POINTER(DDObserveParams)]),
+    "dd_observe_work": (ctypes.c_size_t, [ctypes.c_int]),
+    "dd_observe": (ctypes.c_int, [ctypes.POINTER(DDDetections), c_void_p, ctypes.c_int,
+                                  ctypes.POINTER(DDObserveParams), ctypes.POINTER(DDAreaParams), c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dd_detections_from_agents": (ctypes.c_int, [c_void_p, c_void_p, c_void_p, ctypes.c_int, ctypes.c_int,
+                                                 ctypes.c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dd_set_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_set_schedule": (ctypes.c_int, [c_void_p, ctypes.c_int]),
     "dd_get_gemm_mode": (ctypes.c_int, [c_void_p, ctypes.POINTER(ctypes.c_int)]),

@@ -237,6 +237,29 @@ class DiffusionDriveAgent(_Base):
         return pdm_closed(paths, lead_objects, ego_states, target_velocities, maps, observations, centerlines,
                           device=torch.device("cuda", self._transfuser_model.device), **kwargs)
 
+    def observe(self, detections, ego_states, **kwargs):
+        """PDM's forecasted observation from raw detections on the GPU (``diffusiondrive_amd.simulate.observe``):
+        ``PDMObservation.update`` with ``PDMObjectManager`` (pdm_observation.py:105-205). ``detections``: packed, or as
+        ``pack_detections`` takes them. Returns an ``Observed`` whose ``observations`` and ``lead_objects`` go into
+        ``pdm_score`` and ``pdm_closed_reference`` as they are. Host arguments are packed on and moved to the model's
+        device."""
+        from .simulate import observe
+        return observe(detections, ego_states, device=torch.device("cuda", self._transfuser_model.device), **kwargs)
+
+    def observe_predictions(self, predictions, ego_states, threshold: float = 0.0, **kwargs):
+        """The same from this agent's own agent head: a forward's output dict, of which ``agent_states`` (B, 30, 5) and
+        ``agent_labels`` (B, 30) are read (``detections_from_agent_head``: a box counts where its logit exceeds
+        ``threshold``, at zero velocity), -> detections -> ``Observed``. ``pdm_score(samples, maps,
+        observed.observations, centerlines, ego_states=...)`` then ranks the planner's own draws against what the
+        planner itself sees, with no ground-truth future tracks and nothing leaving the device. Host tensors
+        (``forward`` returns its outputs on the CPU) are moved to the model's device."""
+        from .simulate import detections_from_agent_head, observe
+        dev = torch.device("cuda", self._transfuser_model.device)
+        states = torch.as_tensor(predictions["agent_states"]).to(dev, torch.float32)
+        labels = torch.as_tensor(predictions["agent_labels"]).to(dev, torch.float32)
+        ego = torch.as_tensor(ego_states).to(dev)
+        return observe(detections_from_agent_head(states, labels, ego, threshold), ego, **kwargs)
+
 
 # Hydra configs of the reference name the class TransfuserAgent (diffusiondrive_agent.yaml:1-3).
 TransfuserAgent = DiffusionDriveAgent

@@ -27,6 +27,8 @@ struct dd_centerlines;
 struct dd_paths;
 struct dd_lead_objects;
 struct dd_idm_params;
+struct dd_detections;
+struct dd_observe_params;
 
 namespace ddmi {
 
@@ -681,5 +683,15 @@ void launch_proposals(const dd_paths& paths, const dd_lead_objects& obs, const d
 void launch_pdm_select(const double* score, const double* raw_progress, const double* no_collision,
                        const double* drivable_area, const double* states, int G, int per_group, int32_t* out_index,
                        double* out_states, double* out_reference, hipStream_t st);
+
+// ---- observe.hip: PDM's forecasted observation from raw detections (dd_observe) and the detections of the agent head
+// (dd_detections_from_agents); work = observe_work_doubles(D) doubles. The parameters are checked by the caller.
+size_t observe_work_doubles(int D);
+void launch_observe(const dd_detections& det, const double* ego_states, int G, const dd_observe_params& p,
+                    const dd_area_params& ap, double* work, double* out_boxes, uint8_t* out_valid, double* out_heading,
+                    double* out_speed, uint8_t* out_flags, int32_t* out_order, uint8_t* out_collided, hipStream_t st);
+void launch_detections_from_agents(const float* agent_states, const float* agent_labels, const double* ego_states,
+                                   int B, int A, float threshold, double* out_boxes, uint8_t* out_type,
+                                   int32_t* out_scene_det_off, hipStream_t st);
 
 }  // namespace ddmi

@@ -3008,6 +3008,99 @@ int dd_pdm_select(const double* score, const double* raw_progress, const double*
   });
 }
 
+// ---- PDM's forecasted observation from raw detections (observe.hip): stateless, every argument checked before any
+// device work
+void dd_default_observe_params(dd_observe_params* p) {
+  if (!p) return;
+  p->map_radius = 100.0;
+  p->dt = 0.1;
+  p->num_samples = 50;
+  p->sample_res = 2;
+  p->max_vehicles = 50;
+  p->max_pedestrians = 25;
+  p->max_bicycles = 10;
+  p->max_static = 50;
+  p->stopped_speed = 5e-2;
+}
+
+size_t dd_observe_work(int D) { return ddmi::observe_work_doubles(D); }
+
+int dd_observe(const dd_detections* det, const double* ego_states, int G, const dd_observe_params* op,
+               const dd_area_params* ap, double* work, double* out_boxes, uint8_t* out_valid, double* out_heading,
+               double* out_speed, uint8_t* out_flags, int32_t* out_order, uint8_t* out_collided, void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_observe: " + what); };
+    if (G <= 0) bad("G = " + std::to_string(G) + " must be positive");
+    if (!det) bad("det is null");
+    if (!ego_states) bad("ego_states is null");
+    if (!op) bad("params is null");
+    if (!ap) bad("area_params is null");
+    if (det->num_dets < 0) bad("dd_detections.num_dets = " + std::to_string(det->num_dets) + " is negative");
+    if (!det->scene_det_off) bad("dd_detections.scene_det_off is null");
+    if (det->num_dets > 0) {
+      if (!det->boxes) bad("dd_detections.boxes is null");
+      if (!det->type) bad("dd_detections.type is null");
+      if (!work) bad("work is null");
+      if (!out_boxes) bad("out_boxes is null");
+      if (!out_valid) bad("out_valid is null");
+      if (!out_heading) bad("out_heading is null");
+      if (!out_speed) bad("out_speed is null");
+      if (!out_flags) bad("out_flags is null");
+      if (!out_order) bad("out_order is null");
+      if (!out_collided) bad("out_collided is null");
+      if (reinterpret_cast<uintptr_t>(out_boxes) % 16) bad("out_boxes is not 16-byte aligned");
+      if (det->collided_in == out_collided) bad("dd_detections.collided_in is out_collided");
+    }
+    if (op->num_samples < 1) bad("dd_observe_params.num_samples = " + std::to_string(op->num_samples) + " must be positive");
+    if (op->sample_res < 1 || op->sample_res > op->num_samples)
+      bad("dd_observe_params.sample_res = " + std::to_string(op->sample_res) + " must be in 1..num_samples = " +
+          std::to_string(op->num_samples));
+    const long long t_obs = (long long)op->num_samples + op->sample_res;
+    if (t_obs < 50)
+      bad("dd_observe_params.num_samples + sample_res = " + std::to_string(t_obs) + " is below 50 (TTC reads map t + 9)");
+    if (t_obs * det->num_dets * 8 >= (1LL << 31))
+      bad("dd_detections.num_dets = " + std::to_string(det->num_dets) + " x " + std::to_string(t_obs) +
+          " times do not fit the int32 offsets");
+    const struct { const char* field; int v; } caps[] = {{"max_vehicles", op->max_vehicles},
+                                                         {"max_pedestrians", op->max_pedestrians},
+                                                         {"max_bicycles", op->max_bicycles},
+                                                         {"max_static", op->max_static}};
+    for (const auto& f : caps)
+      if (f.v < 0) bad(std::string("dd_observe_params.") + f.field + " = " + std::to_string(f.v) + " is negative");
+    const struct { const char* field; double v; } figures[] = {{"dd_observe_params.dt", op->dt},
+                                                               {"dd_observe_params.map_radius", op->map_radius},
+                                                               {"dd_observe_params.stopped_speed", op->stopped_speed},
+                                                               {"dd_area_params.half_length", ap->half_length},
+                                                               {"dd_area_params.half_width", ap->half_width},
+                                                               {"dd_area_params.rear_axle_to_center", ap->rear_axle_to_center}};
+    for (const auto& f : figures)
+      if (!std::isfinite(f.v) || f.v < 0.0)
+        bad(std::string(f.field) + " = " + std::to_string(f.v) + " must be finite and not negative");
+    ddmi::launch_observe(*det, ego_states, G, *op, *ap, work, out_boxes, out_valid, out_heading, out_speed, out_flags,
+                         out_order, out_collided, static_cast<hipStream_t>(stream));
+  });
+}
+
+int dd_detections_from_agents(const float* agent_states, const float* agent_labels, const double* ego_states, int B,
+                              int A, float threshold, double* out_boxes, uint8_t* out_type, int32_t* out_scene_det_off,
+                              void* stream) {
+  return guarded([&] {
+    auto bad = [&](const std::string& what) { throw std::invalid_argument("dd_detections_from_agents: " + what); };
+    if (B <= 0) bad("B = " + std::to_string(B) + " must be positive");
+    if (A <= 0) bad("A = " + std::to_string(A) + " must be positive");
+    if ((long long)B * A >= (1LL << 31)) bad("A B = " + std::to_string((long long)B * A) + " does not fit int32");
+    if (!agent_states) bad("agent_states is null");
+    if (!agent_labels) bad("agent_labels is null");
+    if (!ego_states) bad("ego_states is null");
+    if (!out_boxes) bad("out_boxes is null");
+    if (!out_type) bad("out_type is null");
+    if (!out_scene_det_off) bad("out_scene_det_off is null");
+    if (threshold != threshold) bad("threshold is NaN");
+    ddmi::launch_detections_from_agents(agent_states, agent_labels, ego_states, B, A, threshold, out_boxes, out_type,
+                                        out_scene_det_off, static_cast<hipStream_t>(stream));
+  });
+}
+
 int dd_set_profiling(dd_handle* h, int enable) {
   return guarded([&] {
     if (!h) throw std::invalid_argument("null handle");

@@ -24,7 +24,8 @@ the feature building and the forward batched on the GPU:
   features, launching its forward or finishing it marks that batch's tokens failed (``self.failed``)
   and the other batches - those already in flight on other lanes included - complete.
 
-PDM scoring stays on the CPU (``pdm_score``, out of scope): feed it the returned trajectories.
+PDM scoring is not part of the runner: ``diffusiondrive_amd.simulate`` scores the returned trajectories on the device
+(``simulate_trajectories`` -> ``pdm_score``, against ``observe``'s forecast of the scene's detections).
 """
 import collections
 from typing import Callable, Dict, Iterable, List, Optional, Tuple

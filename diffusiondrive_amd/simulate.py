@@ -12,8 +12,11 @@ on the device (``dd_comfort``: the six flags of ``ego_is_comfortable``, pdm_comf
 packed by ``pack_observations`` (``dd_collisions``: :293-349 and :414-498), ``progress`` the raw progress along the
 centerlines packed by ``pack_centerlines`` (``dd_progress``: :398-412), ``aggregate`` combines the sub-scores
 (``dd_pdm_aggregate``: ``_aggregate_scores``, :156-183), and ``pdm_score`` chains all of it on one stream, so that
-candidates are ranked by PDM score without leaving the device. There is no CPU fallback: a missing library or device
-raises.
+candidates are ranked by PDM score without leaving the device. ``generate_proposals`` / ``pdm_closed`` run PDM-Closed's
+candidate stage in front of it (``dd_proposals``), and ``observe`` builds the forecasted observation both read from the
+current detections (``dd_observe``: ``PDMObservation.update``, pdm_observation.py:105-205), packed by
+``pack_detections`` or taken from the agent head by ``detections_from_agent_head``. There is no CPU fallback: a missing
+library or device raises.
 """
 import ctypes
 from typing import Mapping, NamedTuple, Optional, Sequence, Tuple, Union
@@ -1124,3 +1127,304 @@ def pdm_closed(paths, lead_objects, ego_states: torch.Tensor, target_velocities,
                            area_params=area_params, score_params=score_params, stream=s)
         index, best, reference = select_best(scores, states, stream=s)
     return PDMClosed(scores, index, best, reference, made.proposals, states)
+
+
+# ---- PDM's forecasted observation from raw detections (dd_observe) and the agent head's detections
+
+DET_VEHICLE, DET_PEDESTRIAN, DET_BICYCLE, DET_STATIC, DET_SKIP = 0, 1, 2, 3, 255   # dd_detections.type
+# nuPlan's TrackedObjectType names, quoted from memory (include/ddmi.h): the three AGENT_TYPES, the static types, EGO
+DETECTION_TYPE_NAMES = {"VEHICLE": DET_VEHICLE, "PEDESTRIAN": DET_PEDESTRIAN, "BICYCLE": DET_BICYCLE,
+                        "TRAFFIC_CONE": DET_STATIC, "BARRIER": DET_STATIC, "CZONE_SIGN": DET_STATIC,
+                        "GENERIC_OBJECT": DET_STATIC, "EGO": DET_SKIP}
+NUM_AGENT_BOXES = 30   # the agent head's boxes per scene (transfuser_config.py: num_bounding_boxes)
+
+
+class PackedDetections(NamedTuple):
+    """``dd_detections``: the raw detections of G scenes as flat device tensors (include/ddmi.h)."""
+    boxes: torch.Tensor           # float64 (D, 7): center x, y, heading, length, width, velocity x, y
+    type: torch.Tensor            # uint8 (D): 0 VEHICLE, 1 PEDESTRIAN, 2 BICYCLE, 3 static, 255 EGO / skip
+    scene_det_off: torch.Tensor   # int32 (G + 1)
+    tokens: Tuple[Tuple[str, ...], ...]   # per scene, the detections' tokens in order (host only)
+
+
+class Observed(NamedTuple):
+    """``observe``'s result: the same device tensors seen as what the scorer and the generator take."""
+    observations: PackedObservations    # for pdm_score / collisions / pdm_closed; its ``tokens`` is ()
+    lead_objects: PackedLeadObjects     # for generate_proposals / pdm_closed; its ``tokens`` is ()
+    order: torch.Tensor                 # int32 (K = D): the detection index each slot holds
+    collided: torch.Tensor              # uint8 (D), detection order: what the next call's ``collided`` takes
+    detection_tokens: Tuple[Tuple[str, ...], ...]   # the detections' tokens (host only)
+    ring_tokens: Tuple[Tuple[str, ...], ...]        # per scene, the names of the stop polygons that were packed
+    ignored_rings: Tuple[Tuple[str, ...], ...]      # per scene, the names of the stop polygons that hold the ego quad
+
+    def tokens(self) -> Tuple[Tuple[str, ...], ...]:
+        """Per scene, the token of every slot in order, then the packed stop polygons' names: the object order
+        ``Proposals.lead_index`` counts in. Reads ``order`` back: the one device read of the stage."""
+        order = self.order.cpu().numpy()
+        flat = [t for scene in self.detection_tokens for t in scene]
+        out, k = [], 0
+        for scene, rings in zip(self.detection_tokens, self.ring_tokens):
+            out.append(tuple(flat[int(d)] for d in order[k:k + len(scene)]) + tuple(rings))
+            k += len(scene)
+        return tuple(out)
+
+
+def _detection_rows(entry, g):
+    """One scene's detections as (token, x, y, heading, length, width, vx, vy, type_name) tuples."""
+    for _ in range(2):   # DetectionsTracks.tracked_objects is a TrackedObjects, whose .tracked_objects is the list
+        entry = getattr(entry, "tracked_objects", entry)
+    rows = []
+    for i, item in enumerate(entry):
+        if hasattr(item, "track_token"):
+            velocity = getattr(item, "velocity", None)   # a static object has none
+            rows.append((item.track_token, item.center.x, item.center.y, item.center.heading, item.box.length,
+                         item.box.width, 0.0 if velocity is None else velocity.x,
+                         0.0 if velocity is None else velocity.y, item.tracked_object_type.name))
+            continue
+        try:
+            token, x, y, heading, length, width, vx, vy, type_name = item
+        except (TypeError, ValueError):
+            raise ValueError(f"scene {g} detection {i}: expected (token, x, y, heading, length, width, vx, vy, "
+                             "type_name) or a TrackedObject") from None
+        rows.append((token, x, y, heading, length, width, vx, vy, type_name))
+    return rows
+
+
+def pack_detections(scenes: Sequence, device) -> PackedDetections:
+    """The raw detections of G scenes -> the flat tensors ``dd_observe`` reads, on ``device``. One entry per scene: a
+    list of ``(token, x, y, heading, length, width, vx, vy, type_name)`` - the box's center pose and size, the
+    velocity (0, 0 for a static object) and nuPlan's ``TrackedObjectType`` name - or a duck-typed ``DetectionsTracks``
+    / list of ``TrackedObject``, read only through ``track_token``, ``center.x`` / ``.y`` / ``.heading``,
+    ``box.length`` / ``.width``, ``velocity.x`` / ``.y`` where present and ``tracked_object_type.name``. Raises
+    ``ValueError`` on a non-finite value, a non-positive length or width, a duplicate token within a scene or an
+    unknown type name: the device trusts these arrays."""
+    boxes, types, off, tokens = [], [], [0], []
+    for g, entry in enumerate(scenes):
+        names = []
+        seen = set()
+        for i, (token, *figures, type_name) in enumerate(_detection_rows(entry, g)):
+            if type_name not in DETECTION_TYPE_NAMES:
+                raise ValueError(f"scene {g} detection {i} ({token!r}): unknown type name {type_name!r}")
+            row = np.asarray(figures, dtype=np.float64)
+            if not np.isfinite(row).all():
+                raise ValueError(f"scene {g} detection {i} ({token!r}): non-finite value")
+            if not (row[3] > 0.0 and row[4] > 0.0):
+                raise ValueError(f"scene {g} detection {i} ({token!r}): non-positive length or width")
+            if token in seen:
+                raise ValueError(f"scene {g} detection {i}: duplicate token {token!r}")
+            seen.add(token)
+            boxes.append(row), types.append(DETECTION_TYPE_NAMES[type_name]), names.append(token)
+        off.append(len(types))
+        tokens.append(tuple(names))
+    dev = torch.device(device)
+    b = np.stack(boxes) if boxes else np.zeros((0, 7))
+    return PackedDetections(torch.from_numpy(np.ascontiguousarray(b)).to(dev),
+                            torch.from_numpy(np.asarray(types, dtype=np.uint8)).to(dev),
+                            torch.from_numpy(np.asarray(off, dtype=np.int32)).to(dev), tuple(tokens))
+
+
+def default_observe_params(lib=None) -> _lib.DDObserveParams:
+    """``dd_default_observe_params``: the radius 100 m, dt 0.1 s, 50 samples at resolution 2 (T_obs = 52), the caps 50
+    vehicles / 25 pedestrians / 10 bicycles / 50 static objects, the stopped speed 5e-2 m/s."""
+    p = _lib.DDObserveParams()
+    (lib or _lib.load()).dd_default_observe_params(ctypes.byref(p))
+    return p
+
+
+def _observe_params(params: Union[None, _lib.DDObserveParams, Mapping], lib) -> _lib.DDObserveParams:
+    if isinstance(params, _lib.DDObserveParams):
+        return params
+    p = default_observe_params(lib)
+    for k, v in (params or {}).items():
+        if k not in dict(p._fields_):
+            raise ValueError(f"unknown observe parameter {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+def ego_quad(pose, half_length: float, half_width: float, rear_axle_to_center: float) -> np.ndarray:
+    """The ego quad (4, 2) of a rear-axle pose (x, y, heading) by ``dd_ego_areas``' corner formulas, on the host."""
+    x, y, h = (float(v) for v in pose)
+    cos, sin = np.cos(h), np.sin(h)
+    cx, cy = x + rear_axle_to_center * cos, y + rear_axle_to_center * sin
+    cq, sq = np.cos(h + np.pi / 2.0), np.sin(h + np.pi / 2.0)
+    return np.array([[cx + ((lat * cq) + (lon * cos)), cy + ((lat * sq) + (lon * sin))]
+                     for lon, lat in ((half_length, half_width), (-half_length, half_width),
+                                      (-half_length, -half_width), (half_length, -half_width))])
+
+
+def ring_holds_quad(ring, quad) -> bool:
+    """The rule by which ``observe`` ignores a red light (pdm_observation.py:196-201, ``ego_polygon.within(light)``):
+    all four corners of the quad lie strictly inside the ring (the even-odd crossing count of ``dd_ego_areas``, on
+    differences against the corner: a corner on the ring is outside) and no edge of the ring meets an edge of the quad
+    (closed: touching counts as meeting). A ring that only touches or cuts the quad, or lies apart from it, is kept."""
+    v = _ring(ring, "stop polygon")
+    q = np.asarray(quad, dtype=np.float64)
+    w = np.roll(v, -1, axis=0)
+    for px, py in q:
+        a, b, c, d = v[:, 0] - px, v[:, 1] - py, w[:, 0] - px, w[:, 1] - py
+        cross = (c - a) * (0.0 - b) - (0.0 - a) * (d - b)
+        on_edge = (cross == 0.0) & (np.minimum(a, c) <= 0.0) & (np.maximum(a, c) >= 0.0) \
+            & (np.minimum(b, d) <= 0.0) & (np.maximum(b, d) >= 0.0)
+        flips = ((b > 0.0) != (d > 0.0)) & np.where(d > b, cross > 0.0, cross < 0.0)
+        if on_edge.any() or not (int(flips.sum()) & 1):
+            return False
+
+    def side(ox, oy, ax, ay, bx, by):   # the orientation of (b - o) against (a - o), on differences
+        return np.sign((ax - ox) * (by - oy) - (ay - oy) * (bx - ox))
+
+    for i in range(4):
+        p0, p1 = q[i], q[(i + 1) % 4]
+        for e0, e1 in zip(v, w):
+            d1, d2 = side(*p0, *p1, *e0), side(*p0, *p1, *e1)
+            d3, d4 = side(*e0, *e1, *p0), side(*e0, *e1, *p1)
+            if d1 * d2 < 0 and d3 * d4 < 0:
+                return False
+            if 0 in (d1, d2, d3, d4):   # collinear somewhere: met if the bounding boxes of the two edges overlap
+                if (max(min(p0[0], p1[0]), min(e0[0], e1[0])) <= min(max(p0[0], p1[0]), max(e0[0], e1[0]))
+                        and max(min(p0[1], p1[1]), min(e0[1], e1[1])) <= min(max(p0[1], p1[1]), max(e0[1], e1[1]))
+                        and d1 * d2 <= 0 and d3 * d4 <= 0):
+                    return False
+    return True
+
+
+def split_stop_polygons(stop_polygons: Sequence, ego_states, half_length: float, half_width: float,
+                        rear_axle_to_center: float):
+    """Per scene the stop polygons ``observe`` packs and the names of those it ignores (``ring_holds_quad``). The ring
+    ``i`` of a scene is named ``red_light_<i>``, as ``pack_lead_objects`` names it; a kept ring keeps its name.
+    ``ego_states``: host (G, >= 3) rear-axle poses."""
+    ego = np.asarray(ego_states, dtype=np.float64)
+    kept, names, ignored = [], [], []
+    for g, rings in enumerate(stop_polygons):
+        quad = ego_quad(ego[g, :3], half_length, half_width, rear_axle_to_center)
+        kept.append([]), names.append([]), ignored.append([])
+        for i, ring in enumerate(rings):
+            name = f"{RED_LIGHT_TOKEN}_{i}"
+            if ring_holds_quad(ring, quad):
+                ignored[-1].append(name)
+            else:
+                kept[-1].append(_ring(ring, f"scene {g} stop polygon {i}")), names[-1].append(name)
+    return kept, tuple(tuple(n) for n in names), tuple(tuple(n) for n in ignored)
+
+
+def observe(detections, ego_states: torch.Tensor, *, collided: Optional[torch.Tensor] = None,
+            stop_polygons: Optional[Sequence] = None, params=None, area_params=None,
+            stream: Optional[torch.cuda.Stream] = None, device=None) -> Observed:
+    """``PDMObservation.update`` with ``PDMObjectManager`` (pdm_observation.py:105-205) on the device: from the current
+    detections and the ego states (G, 11) to the forecasted observation the scorer and the generator read. The ego, far
+    (``map_radius``) and previously collided objects are dropped; the nearest 50 static objects, 50 vehicles, 25
+    pedestrians and 10 bicycles are kept; every kept agent is forecast at constant velocity along its own axis on a
+    0.2 s grid for 5.2 s; what already overlaps the ego quad is recorded in ``collided`` and is valid at no time
+    (include/ddmi.h has the rules at length). ``detections``: ``pack_detections``' or
+    ``detections_from_agent_head``'s result (or what ``pack_detections`` takes: packed here). ``collided``: the
+    ``Observed.collided`` of the call before on the same detections, or None. ``stop_polygons[g]``: the scene's
+    red-light rings, host data as ``pack_lead_objects`` takes them; a ring that holds the whole ego quad
+    (``ring_holds_quad``) is ignored, as the reference ignores such a light from then on, and named in
+    ``ignored_rings`` - with stop polygons the ego poses are read back to the host for that test. ``params``: a
+    ``DDObserveParams`` or a mapping of overrides of ``default_observe_params()``. Scene g's tracks are its
+    detections' slots: K = D, a dropped detection is a track valid at no time, and no count returns to the host.
+    Returns an ``Observed``; both packed results share their tensors and go into ``pdm_score``, ``collisions``,
+    ``generate_proposals`` and ``pdm_closed`` as they are. A bad argument raises ``ValueError`` with
+    ``dd_last_error()``'s text."""
+    lib = _lib.load()
+    dev = None
+    for t in (detections.boxes if isinstance(detections, PackedDetections) else None,
+              ego_states if isinstance(ego_states, torch.Tensor) else None):
+        if t is not None and t.device.type == "cuda":
+            dev = t.device
+            break
+    if dev is None:
+        dev = torch.device("cuda" if device is None else device)
+    if dev.type == "cuda" and dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(detections, PackedDetections):
+        detections = pack_detections(detections, dev)
+    _fields_on(detections, (torch.float64, torch.uint8, torch.int32), dev, "detections")
+    ego = _ego(ego_states, dev)
+    scenes = int(ego.shape[0])
+    d = int(detections.type.numel())
+    if int(detections.scene_det_off.numel()) != scenes + 1:
+        raise ValueError(f"detections hold {int(detections.scene_det_off.numel()) - 1} scenes for {scenes} (the rows of "
+                         "ego_states)")
+    if tuple(detections.boxes.shape) != (d, 7):
+        raise ValueError(f"detections.boxes must be ({d}, 7), got {tuple(detections.boxes.shape)}")
+    if collided is not None and (not isinstance(collided, torch.Tensor) or collided.device != dev
+                                 or collided.dtype != torch.uint8 or tuple(collided.shape) != (d,)
+                                 or not collided.is_contiguous()):
+        raise ValueError(f"collided must be a contiguous uint8 ({d},) tensor on {dev} (an Observed.collided)")
+    p, ap = _observe_params(params, lib), _area_params(area_params, lib)
+    t_obs = int(p.num_samples) + int(p.sample_res)
+    kept_rings = [[] for _ in range(scenes)]
+    ring_names = ignored = tuple(() for _ in range(scenes))
+    if stop_polygons is not None:
+        if len(stop_polygons) != scenes:
+            raise ValueError(f"stop_polygons holds {len(stop_polygons)} scenes for {scenes}")
+        kept_rings, ring_names, ignored = split_stop_polygons(stop_polygons, ego[:, :3].cpu().numpy(), ap.half_length,
+                                                              ap.half_width, ap.rear_axle_to_center)
+    verts, ring_off, scene_ring_off = [], [0], [0]
+    for rings in kept_rings:
+        for ring in rings:
+            verts.append(ring)
+            ring_off.append(ring_off[-1] + ring.shape[0])
+        scene_ring_off.append(len(ring_off) - 1)
+    det = _lib.DDDetections(detections.boxes.data_ptr() or None, detections.type.data_ptr() or None,
+                            detections.scene_det_off.data_ptr() or None,
+                            collided.data_ptr() or None if collided is not None else None, d)
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):  # the outputs and the scratch belong to the stream that runs
+        boxes = torch.empty((d, max(t_obs, 0), 4, 2), dtype=torch.float64, device=dev)
+        valid = torch.empty((d, max(t_obs, 0)), dtype=torch.uint8, device=dev)
+        heading = torch.empty((d,), dtype=torch.float64, device=dev)
+        speed = torch.empty((d,), dtype=torch.float64, device=dev)
+        flags = torch.empty((d,), dtype=torch.uint8, device=dev)
+        order = torch.empty((d,), dtype=torch.int32, device=dev)
+        out_collided = torch.empty((d,), dtype=torch.uint8, device=dev)
+        work = torch.empty((lib.dd_observe_work(d),), dtype=torch.float64, device=dev)
+        rc = lib.dd_observe(ctypes.byref(det), ego.data_ptr(), scenes, ctypes.byref(p), ctypes.byref(ap),
+                            work.data_ptr(), boxes.data_ptr() or None, valid.data_ptr() or None,
+                            heading.data_ptr() or None, speed.data_ptr() or None, flags.data_ptr() or None,
+                            order.data_ptr() or None, out_collided.data_ptr() or None, s.cuda_stream)
+        _raise(rc, lib)
+        f64 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(dev)  # noqa: E731
+        i32 = lambda a: torch.from_numpy(np.asarray(a, dtype=np.int32)).to(dev)  # noqa: E731
+        stop_verts = f64(np.concatenate(verts) if verts else np.zeros((0, 2)))
+        rings_dev, scene_rings_dev = i32(ring_off), i32(scene_ring_off)
+    off = detections.scene_det_off
+    return Observed(PackedObservations(boxes, valid, heading, flags, off, ()),
+                    PackedLeadObjects(boxes, valid, heading, speed, off, stop_verts, rings_dev, scene_rings_dev, ()),
+                    order, out_collided, detections.tokens, ring_names, ignored)
+
+
+def detections_from_agent_head(agent_states: torch.Tensor, agent_labels: torch.Tensor, ego_states: torch.Tensor,
+                               threshold: float = 0.0, stream: Optional[torch.cuda.Stream] = None) -> PackedDetections:
+    """``dd_detections_from_agents``: the planner's own agent head as detections. ``agent_states`` device float32
+    (B, A, 5) - ego-frame x, y, heading, length, width (transfuser_features.py:192-204) - and ``agent_labels`` float32
+    (B, A) logits, exactly what a forward writes, read in place; ``ego_states`` (B, 11) float64. A box is a VEHICLE
+    where its logit exceeds ``threshold`` (0 = the callback's ``sigmoid() > 0.5``), its length and width are positive
+    and every value is finite; any other row is zeroed and skipped. The center is the rear-axle pose composed with
+    (x, y), the heading the ego's plus the box's, the velocity 0: such a track is flagged stopped and forecast in
+    place. The tokens are ``agent_<a>``."""
+    lib = _lib.load()
+    if not isinstance(agent_states, torch.Tensor) or agent_states.device.type != "cuda":
+        raise ValueError("agent_states must be a device tensor (a forward's agent_states)")
+    dev = agent_states.device
+    if agent_states.dtype != torch.float32 or agent_states.dim() != 3 or agent_states.shape[2] != 5:
+        raise ValueError(f"agent_states must be float32 (B, A, 5), got {tuple(agent_states.shape)} {agent_states.dtype}")
+    b, a = int(agent_states.shape[0]), int(agent_states.shape[1])
+    if not isinstance(agent_labels, torch.Tensor) or agent_labels.device != dev or agent_labels.dtype != torch.float32 \
+            or tuple(agent_labels.shape) != (b, a):
+        raise ValueError(f"agent_labels must be a float32 ({b}, {a}) tensor on {dev}")
+    agent_states, agent_labels = agent_states.contiguous(), agent_labels.contiguous()
+    ego = _ego(ego_states, dev)
+    if int(ego.shape[0]) != b:
+        raise ValueError(f"ego_states holds {int(ego.shape[0])} scenes for {b} (the first dimension of agent_states)")
+    s = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.device(dev), torch.cuda.stream(s):
+        boxes = torch.empty((b * a, 7), dtype=torch.float64, device=dev)
+        types = torch.empty((b * a,), dtype=torch.uint8, device=dev)
+        off = torch.empty((b + 1,), dtype=torch.int32, device=dev)
+        rc = lib.dd_detections_from_agents(agent_states.data_ptr() or None, agent_labels.data_ptr() or None,
+                                           ego.data_ptr() or None, b, a, float(threshold), boxes.data_ptr() or None,
+                                           types.data_ptr() or None, off.data_ptr(), s.cuda_stream)
+    _raise(rc, lib)
+    return PackedDetections(boxes, types, off, tuple(tuple(f"agent_{i}" for i in range(a)) for _ in range(b)))

@@ -681,6 +681,100 @@ int dd_pdm_select(const double* score, const double* raw_progress, const double*
                   const double* drivable_area, const double* states, int N, int per_group, int32_t* out_index,
                   double* out_states, double* out_reference, void* stream);
 
+/* ---- PDM's forecasted observation from raw detections (PDMObservation.update, pdm_observation.py:105-205, with
+ * PDMObjectManager, pdm_object_manager.py) on the GPU: the stage in front of dd_proposals and dd_collisions ---- */
+/* The detections of G scenes as flat device arrays, scene g = rows scene_det_off[g] .. [g + 1] - 1. TRUSTED, not
+ * validated (diffusiondrive_amd.simulate.pack_detections guarantees it): scene_det_off starts at 0, never decreases
+ * and ends at num_dets; every row whose type is 0..3 is finite with a positive length and width. */
+#define DD_DET_VEHICLE 0
+#define DD_DET_PEDESTRIAN 1
+#define DD_DET_BICYCLE 2
+#define DD_DET_STATIC 3     /* every tracked object type that is not in nuPlan's AGENT_TYPES */
+#define DD_DET_SKIP 255     /* TrackedObjectType.EGO, or a row to pass over; so is every value of 4..254 */
+typedef struct dd_detections {
+  const double* boxes;             /* device double (D, 7): center x, y, heading, length, width, velocity x, y */
+  const uint8_t* type;             /* device uint8 (D): DD_DET_* */
+  const int32_t* scene_det_off;    /* device int32 (G + 1) */
+  const uint8_t* collided_in;      /* device uint8 (D) or NULL: non-zero = the track is in collided_track_ids (the
+                                      collided_out of the call before); it must not be the call's collided_out */
+  int num_dets;                    /* D, the host's copy of scene_det_off[G]; with D = 0 the first two may be NULL */
+} dd_detections;
+typedef struct dd_observe_params {
+  double map_radius;     /* 100 m (metric_cache_processor.py:46); 0 = no radius filter (`self._map_radius and ...`) */
+  double dt;             /* 0.1 s (the sampling's interval_length) */
+  int num_samples;       /* 50: _observation_samples */
+  int sample_res;        /* 2: observation_sample_res; T_obs = num_samples + sample_res */
+  int max_vehicles;      /* 50 (MAX_DYNAMIC_OBJECTS) */
+  int max_pedestrians;   /* 25 */
+  int max_bicycles;      /* 10 */
+  int max_static;        /* 50 (MAX_STATIC_OBJECTS) */
+  double stopped_speed;  /* 5e-2 m/s: at or below it an agent counts as stopped (dd_observations.flags bit 0) */
+} dd_observe_params;
+/* Fill *p with the values listed above. */
+void dd_default_observe_params(dd_observe_params* p);
+/* Device scratch of dd_observe over D detections, in doubles (per slot the box at t = 0, its displacement per second
+ * and whether it is valid). Never 0. */
+size_t dd_observe_work(int D);
+/* ego_states: device double (G, 11) in StateIndex order (the rear-axle x, y, heading are read). The rules:
+ *   ego center = rear axle + rear_axle_to_center (cos h, sin h); the ego quad is dd_ego_areas' four corners there.
+ *   dropped: a type outside 0..3, a row with collided_in set, and - unless map_radius is 0 - a row with
+ *     hypot(ego center - center) > map_radius. nuPlan's Point2D.distance_to is quoted from memory as that hypot;
+ *     nuPlan is not part of this tree.
+ *   corners of a row: center + (lat cos(h + pi/2) + lon cos h, lat sin(h + pi/2) + lon sin h), lon = +-length / 2,
+ *     lat = +-width / 2, in the order front-left, rear-left, rear-right, front-right: the formula dd_ego_areas uses for
+ *     nuPlan's translate_longitudinally_and_laterally (the cosine of the rounded sum, not -sin h), which
+ *     OrientedBox.all_corners is remembered to call.
+ *   agents (types 0..2; pdm_object_manager.py:62-79): velocity_angle = atan2(vy, vx); the agent drives forward iff
+ *     |normalize(h - velocity_angle)| < pi / 2, normalize(a) = atan2(sin a, cos a); track_heading = h, or
+ *     normalize(h + pi) when it does not; dxy = (cos, sin)(track_heading) * hypot(vx, vy): a reversing agent is forecast
+ *     backwards along its own axis, never along its velocity. A static object has dxy = 0.
+ *   selection per class (static; vehicles; pedestrians; bicycles): ascending ((cx - px)^2 + (cy - py)^2)^0.5 to the
+ *     ego center, the first `cap` kept; a tie goes to the lower detection index (the reference's np.argsort is an
+ *     unstable introsort: its order on a tie is not defined).
+ *   slots: scene g's tracks are slots scene_det_off[g] .. [g + 1] - 1, so K = D and scene_track_off = scene_det_off,
+ *     and no count returns to the host. Within the scene, in the reference's token order (static + dynamic,
+ *     pdm_observation.py:186, which decides dd_proposals' tie rule and out_lead_index): the kept static objects by
+ *     distance, the kept vehicles, pedestrians, bicycles, then every dropped row in detection order. A dropped row is a
+ *     track that is valid at no time; dd_collisions and dd_proposals honour `valid`.
+ *   boxes[k, t] = corners + (double(sample_res (t / sample_res)) dt) dxy, t = 0 .. T_obs - 1: what observation[t]
+ *     returns through _global_to_local_idcs (map t / sample_res, forecast to sample_res (t / sample_res) dt).
+ *   newly collided: a kept track whose box at t = 0 meets the ego quad (dd_collisions' closed separating-axis test on
+ *     differences against the ego quad's first corner). It counted toward its cap - the reference appends the token
+ *     after the maps are built - and is invalid at every time, because the scorer and the generator skip
+ *     collided_track_ids. out_collided[d] = collided_in[d] | newly collided, in detection order.
+ * Outputs, which fill a dd_observations and a dd_lead_objects that share boxes, valid and heading:
+ *   out_boxes: device double (K, T_obs, 4, 2), 16-byte aligned; zero where the track is not valid
+ *   out_valid: device uint8 (K, T_obs)
+ *   out_heading: device double (K): the row's own heading (unique_objects[token].center.heading)
+ *   out_speed: device double (K): hypot(vx, vy), 0 for a type outside 0..2
+ *   out_flags: device uint8 (K): bit 0 stopped (no agent, or speed <= stopped_speed), bit 1 agent (types 0..2)
+ *   out_order: device int32 (K): the detection index (0 .. D - 1) each slot holds
+ *   out_collided: device uint8 (D)
+ * Two launches on `stream` (one workgroup per scene ranks by counting within the class over LDS chunks of 256 rows, so
+ * any D works, and writes the slots' t = 0 boxes to `work`; then one thread per corner of the output writes the
+ * forecast in whole cache lines); none with D = 0. No allocation, copy, synchronisation or atomics: two calls are
+ * bit-equal. DD_ERR_INVALID before any device work, naming the argument or field in dd_last_error(): G <= 0, num_dets
+ * < 0, a null det / ego_states / params / area_params / scene_det_off, with num_dets > 0 a null boxes / type / work /
+ * output or an out_boxes that is not 16-byte aligned, collided_in == out_collided, sample_res outside 1..num_samples,
+ * num_samples + sample_res < 50, (num_samples + sample_res) * num_dets * 8 >= 2^31 (the packers' limit), a negative cap, a dt,
+ * map_radius, stopped_speed or vehicle figure (half_length, half_width, rear_axle_to_center) that is negative or
+ * non-finite. */
+int dd_observe(const dd_detections* det, const double* ego_states, int G, const dd_observe_params* params,
+               const dd_area_params* area_params, double* work, double* out_boxes, uint8_t* out_valid,
+               double* out_heading, double* out_speed, uint8_t* out_flags, int32_t* out_order, uint8_t* out_collided,
+               void* stream);
+/* Detections from the planner's own agent head, read in place: agent_states device float (B, A, 5), the ego-frame x,
+ * y, heading, length, width of transfuser_features.py:192-204; agent_labels device float (B, A) logits; ego_states
+ * device double (B, 11). Writes a dd_detections of D = A B rows: out_boxes (D, 7), out_type (D), out_scene_det_off
+ * (B + 1) = A b. Row (b, a), every value widened to double first: center = (x0 + (cos(h0) x - sin(h0) y), y0 +
+ * (sin(h0) x + cos(h0) y)), heading = h0 + h, velocity 0, type VEHICLE where logit > threshold (0 is the callback's
+ * sigmoid() > 0.5), length and width are positive and all six values are finite; any other row is all zeros with type
+ * DD_DET_SKIP. The reference has no counterpart: this is the project's rule. A zero-velocity agent is flagged stopped
+ * and forecast in place. One launch. DD_ERR_INVALID: B <= 0, A <= 0, A B >= 2^31, a null argument, a NaN threshold. */
+int dd_detections_from_agents(const float* agent_states, const float* agent_labels, const double* ego_states, int B,
+                              int A, float threshold, double* out_boxes, uint8_t* out_type,
+                              int32_t* out_scene_det_off, void* stream);
+
 /* ---- input feature builder (TransfuserFeatureBuilder.compute_features on the GPU) ---------- */
 /* Camera feature (transfuser_features.py:57-77): crop + stitch + cv2 INTER_LINEAR resize +
  * ToTensor. cams: device uint8, B scenes x 3 images (cam_l0, cam_f0, cam_r0) x src_h x src_w x 3
